@@ -16,12 +16,19 @@ Run (driver contract):
       --master-addr 127.0.0.1 bench.py --gpus 8 --steps 5 --warmup 2
 
 Synthetic data (seeded GBM, data/synthetic.py), random-init population.
-Outside the timed GA loop the same run also measures (and reports under
-"config"): the CONTINUOUS unsegmented backtest via the time-parallel
-kernel pair (all ranks), and under "secondary": the Monte-Carlo VaR path
-rate (10M correlated-GBM paths x 64 assets), the LSTM-predictor train
-rate (BASELINE #2) and the PPO train rate (BASELINE #4) — so the
-driver's clock attests every BASELINE config.
+A plain run does only what the headline needs: set up, warm up, time the
+steps, print the result line. --dump-outputs DIR additionally writes what
+the last timed generation computed (fitness, evolved population, backtest
+metrics) as DIR/<name>.npy; the inputs are a function of the arguments
+only, so two builds can be compared output for output.
+
+With --full the same run also measures, outside the timed GA loop (and
+reports under "config"): the CONTINUOUS unsegmented backtest via the
+time-parallel kernel pair (all ranks), and under "secondary": the
+Monte-Carlo VaR path rate (10M correlated-GBM paths x 64 assets), the
+LSTM-predictor train rate (BASELINE #2) and the PPO train rate
+(BASELINE #4) — so one clocked run attests every BASELINE config:
+  python bench.py --gpus 1 --steps 5 --warmup 2 --full
 """
 
 from __future__ import annotations
@@ -50,17 +57,30 @@ def parse_args():
     ap.add_argument("--symbols", type=int, default=64)
     ap.add_argument("--candles", type=int, default=1_000_000)
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the continuous backtest and the "
+                         "secondary Monte-Carlo / LSTM / PPO workloads "
+                         "(outside the timed loop)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs as "
+                         "DIR/<name>.npy")
     ap.add_argument("--skip-mc", action="store_true",
-                    help="skip the secondary Monte-Carlo measurement")
+                    help="with --full: skip the secondary Monte-Carlo "
+                         "measurement")
     ap.add_argument("--skip-train", action="store_true",
-                    help="skip the secondary LSTM/PPO train measurements")
+                    help="with --full: skip the secondary LSTM/PPO train "
+                         "measurements")
     ap.add_argument("--skip-continuous", action="store_true",
-                    help="skip the continuous (unsegmented) backtest loop")
+                    help="with --full: skip the continuous (unsegmented) "
+                         "backtest loop")
     ap.add_argument("--segments", type=int, default=64,
                     help="fitness time-CV segments per symbol (64 measured "
                          "fastest; the continuous seg=1 case is measured "
                          "separately via the time-parallel kernel pair)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
+    return args
 
 
 def measure_train(device):
@@ -111,6 +131,46 @@ def measure_mc(device, n_paths=10_000_000, n_assets=64, n_steps=30):
     }
 
 
+DUMP_SAMPLE_BYTES = 32 << 20   # cap on the sampled metrics array
+DUMP_SAMPLE_SEED = 20240607
+
+
+def _as_float_array(t):
+    a = t.detach().cpu().numpy()
+    if a.dtype not in (np.float32, np.float64):
+        a = a.astype(np.float32)
+    return np.ascontiguousarray(a)
+
+
+def dump_outputs(engine, out_dir):
+    """Write what the last GA generation produced (rank 0's view):
+
+    fitness.npy         (world*pop,) global fitness, as all-gathered
+    population.npy      (world*pop, NPARAM) population after evolution
+    metrics_mean.npy    (pop, NMETRIC) f64 lane-mean of the local shard's
+                        backtest metrics — covers every lane
+    metrics_sample.npy  (pop, n, NMETRIC) the metrics of a fixed seeded
+                        subset of the (symbol x segment) lanes; the full
+                        tensor is ~170 MB at the default shape
+    """
+    out_dir = Path(out_dir)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    metrics = engine.last_metrics
+    pop, lanes, nmetric = metrics.shape
+    n = min(lanes, max(DUMP_SAMPLE_BYTES // (pop * nmetric * 4), 1))
+    cols = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(
+        lanes, size=n, replace=False))
+    cols_t = torch.from_numpy(cols).to(metrics.device)
+    arrays = {
+        "fitness": _as_float_array(engine.last_fitness_global),
+        "population": _as_float_array(engine.pop_t),
+        "metrics_mean": _as_float_array(metrics.double().mean(dim=1)),
+        "metrics_sample": _as_float_array(metrics[:, cols_t, :]),
+    }
+    for name, arr in arrays.items():
+        np.save(out_dir / f"{name}.npy", arr)
+
+
 def main():
     args = parse_args()
     rank, world, device = pdist.init_distributed()
@@ -157,11 +217,15 @@ def main():
     total_candle_evals = engine.candle_evals_per_step * world * args.steps
     value = total_candle_evals / elapsed
 
-    # Continuous (unsegmented) fitness: the same GA generation loop with
-    # the time-parallel kernel pair (ops/hip/backtest_tp.hip) — the
-    # multi-year-single-history case, all ranks participating.
+    if args.dump_outputs and rank == 0:
+        dump_outputs(engine, args.dump_outputs)
+
+    # --full only. Continuous (unsegmented) fitness: the same GA
+    # generation loop with the time-parallel kernel pair
+    # (ops/hip/backtest_tp.hip) — the multi-year-single-history case, all
+    # ranks participating.
     continuous = {}
-    if on_gpu and not args.skip_continuous and segments > 1:
+    if args.full and on_gpu and not args.skip_continuous and segments > 1:
         engine_c = GAEngine(
             candles, pop_per_rank=pop, rank=rank, world=world,
             device=device, seed=args.seed + 1, segments=1,
@@ -186,9 +250,9 @@ def main():
         }
 
     secondary = {}
-    if on_gpu and rank == 0 and not args.skip_mc:
+    if args.full and on_gpu and rank == 0 and not args.skip_mc:
         secondary = measure_mc(device)
-    if on_gpu and rank == 0 and not args.skip_train:
+    if args.full and on_gpu and rank == 0 and not args.skip_train:
         secondary.update(measure_train(device))
     pdist.barrier()      # all ranks leave together (rank 0 runs MC above)
 

@@ -661,7 +661,8 @@ def test_code_strategy_cycle_improves_and_registers(tmp_path):
     # registry round-trip
     async def roundtrip():
         bus = InProcessBus()
-        reg = ModelRegistryService(bus)
+        reg = ModelRegistryService(
+            bus, store_path=str(tmp_path / "registry.json"))
         await reg.register(
             "code-cycle-best", "strategy_code",
             params={"quality": res["final_quality"],
