@@ -25,6 +25,7 @@ from ..backtesting.strategy import (
     clip_params, dict_to_params, params_to_dict,
 )
 from ..ops import gpu_available
+from .families import FAMILIES
 from .data_manager import HistoricalDataManager
 
 ANNUAL_CANDLES = 525_600.0      # 1m bars
@@ -37,10 +38,12 @@ INTERVAL_BARS_PER_YEAR = {
 }
 
 
-# Named strategy presets (the reference ships dca/grid/threshold bots as
-# separate services; in backtests they are parameter presets of the same
-# state machine — dca_strategy.py:347-741 / grid semantics approximated by
-# vote cadence + sizing).
+# Named strategy presets of the vote state machine. "dca_strategy" is such
+# a preset (DCA-like cadence and sizing through votes) and is kept for
+# compatibility; the real resting-order grid and scheduled/dip-buy DCA
+# semantics of the reference's bots (grid_trading_strategy.py,
+# dca_strategy.py:347-741) live in the strategy families "grid" and "dca"
+# (backtesting/families.py), which run_backtest() routes to by name.
 STRATEGY_PRESETS = {
     "default": {},
     "dca_strategy": {
@@ -118,12 +121,18 @@ class BacktestEngine:
         df = self.dm.load_market_data(symbol, interval,
                                       n_candles=n_candles)
         candles = self.dm.to_chlv(df.iloc[:n_candles])
-        preset = dict(STRATEGY_PRESETS.get(strategy, {}))
-        if params:
-            preset.update(params)
-        vec = clip_params(dict_to_params(preset)[None])
+        fam = FAMILIES.get(strategy)
+        if fam is not None:
+            vec = fam.clip(fam.dict_to_params(params or {})[None])
+            to_dict = fam.params_to_dict
+        else:
+            preset = dict(STRATEGY_PRESETS.get(strategy, {}))
+            if params:
+                preset.update(params)
+            vec = clip_params(dict_to_params(preset)[None])
+            to_dict = params_to_dict
         t0 = time.perf_counter()
-        out = self._run(candles, vec, record_equity)
+        out = self._run(candles, vec, record_equity, fam)
         elapsed = time.perf_counter() - t0
         metrics = out[0] if record_equity else out
         T = candles.shape[1]
@@ -132,7 +141,7 @@ class BacktestEngine:
             "symbol": symbol, "strategy": strategy, "interval": interval,
             "n_candles": T, "engine": self.device,
             "candles_per_sec": T / max(elapsed, 1e-9),
-            "params": params_to_dict(vec[0]),
+            "params": to_dict(vec[0]),
         })
         if record_equity:
             stats["equity_curve"] = out[1][0, 0].tolist()
@@ -140,18 +149,18 @@ class BacktestEngine:
         return stats
 
     def _run(self, candles: np.ndarray, pop: np.ndarray,
-             record_equity: bool = False):
+             record_equity: bool = False, fam=None):
         if self.device.startswith("cuda") and not record_equity:
             import torch
 
             from ..ops.backtest import run_backtest_gpu
             c = torch.from_numpy(candles).to(self.device)
             p = torch.from_numpy(pop).to(self.device)
-            m = run_backtest_gpu(c, p)
+            m = (fam.run_gpu if fam is not None else run_backtest_gpu)(c, p)
             torch.cuda.synchronize()
             return m.cpu().numpy()
-        return run_backtest_cpu(candles, pop,
-                                record_equity=record_equity)
+        run_cpu = fam.run_cpu if fam is not None else run_backtest_cpu
+        return run_cpu(candles, pop, record_equity=record_equity)
 
     # --- sweeps (reference :127-178) -------------------------------------
     def run_multiple_backtests(self, symbols: list[str],
@@ -172,13 +181,16 @@ class BacktestEngine:
     # --- GA parameter optimization over the GPU kernel -------------------
     def optimize(self, symbol: str, pop_size: int = 256,
                  generations: int = 10, n_candles: int = 20_000,
-                 seed: int = 0) -> dict:
+                 seed: int = 0, strategy: str = "vote") -> dict:
+        """strategy: "vote" (the vote machine) or a family name ("grid",
+        "dca") — the GA then searches that family's parameter space."""
         from .ga_engine import GAEngine
 
         df = self.dm.load_market_data(symbol, n_candles=n_candles)
         candles = self.dm.to_chlv(df.iloc[:n_candles])
         eng = GAEngine(candles, pop_per_rank=pop_size, device=self.device,
-                       seed=seed, segments="auto")
+                       seed=seed, segments="auto", family=strategy)
+        fam = FAMILIES.get(strategy)
         t0 = time.perf_counter()
         history = []
         for _ in range(generations):
@@ -187,9 +199,14 @@ class BacktestEngine:
         eng.eval_fitness()
         elapsed = time.perf_counter() - t0
         fit, best = eng.best()
-        stats = self.run_backtest(symbol, "optimized",
-                                  params=params_to_dict(best),
-                                  n_candles=n_candles)
+        if fam is not None:
+            stats = self.run_backtest(symbol, strategy,
+                                      params=fam.params_to_dict(best),
+                                      n_candles=n_candles)
+        else:
+            stats = self.run_backtest(symbol, "optimized",
+                                      params=params_to_dict(best),
+                                      n_candles=n_candles)
         stats["optimize"] = {
             "pop_size": pop_size, "generations": generations,
             "best_fitness": fit, "fitness_history": history,

@@ -42,8 +42,15 @@ class GAEngine:
         mut_scale: float = 0.1,
         segments: int | str = 1,
         continuous: bool = False,
+        family: str = "vote",
     ):
-        """segments > 1 splits each symbol's history into `segments`
+        """family selects the strategy state machine: "vote" (the
+        19-parameter vote/SL/TP machine of strategy.py, today's code
+        paths) or a family of backtesting/families.py ("grid", "dca"),
+        which brings its own bounds, random population, CPU twin and GPU
+        op. continuous=True is vote-only.
+
+        segments > 1 splits each symbol's history into `segments`
         independent backtest segments (a pure reshape of the candle
         tensor): fitness becomes a time-segmented cross-validation — the
         standard GA anti-overfit practice — AND multiplies backtest-lane
@@ -52,6 +59,14 @@ class GAEngine:
         the SIMDs dependent-latency cover). Total candle-evals per
         generation are unchanged."""
         self.device = torch.device(device)
+        self.family = family
+        self.fam = None
+        if family != "vote":
+            from .families import get_family
+
+            assert not continuous, \
+                "continuous=True is only available for family='vote'"
+            self.fam = get_family(family)
         self.rank, self.world = rank, world
         self.pop_per_rank = pop_per_rank
         self.seed = seed
@@ -86,14 +101,20 @@ class GAEngine:
         self.use_gpu = self.device.type == "cuda"
 
         # full global population replicated (tiny); rank evaluates its slice
-        global_pop = random_population(pop_per_rank * world, seed=seed)
+        if self.fam is None:
+            global_pop = random_population(pop_per_rank * world, seed=seed)
+            bounds = PARAM_BOUNDS
+        else:
+            global_pop = self.fam.random_population(
+                pop_per_rank * world, seed=seed)
+            bounds = self.fam.bounds
         self.pop_t = torch.from_numpy(global_pop).to(self.device)
         if self.use_gpu:
             self.candles_t = torch.from_numpy(
                 np.ascontiguousarray(candles)
             ).to(self.device)
             self.bounds_t = torch.from_numpy(
-                np.ascontiguousarray(PARAM_BOUNDS)
+                np.ascontiguousarray(bounds)
             ).to(self.device)
         else:
             self.candles_np = np.ascontiguousarray(candles)
@@ -107,7 +128,15 @@ class GAEngine:
     def eval_fitness(self) -> torch.Tensor:
         """Backtest the local shard; all-gather to global fitness."""
         shard = self.pop_t[self._my_slice()]
-        if self.use_gpu:
+        if self.fam is not None:
+            if self.use_gpu:
+                metrics = self.fam.run_gpu(self.candles_t, shard)
+                fitness_local = metrics[..., 9].mean(dim=1)
+            else:
+                metrics = torch.from_numpy(self.fam.run_cpu(
+                    self.candles_np, shard.cpu().numpy()))
+                fitness_local = metrics[..., 9].mean(dim=1).to(self.device)
+        elif self.use_gpu:
             if self.continuous:
                 from ..ops.backtest import run_backtest_continuous_gpu
 
@@ -140,7 +169,22 @@ class GAEngine:
         children (same seed/gen), each keeps the full population so no
         parameter broadcast is needed."""
         fitness = self.last_fitness_global
-        if self.use_gpu:
+        if self.fam is not None:
+            kw = dict(
+                elite_k=self.elite_k, tournament=self.tournament,
+                cx_rate=self.cx_rate, mut_rate=self.mut_rate,
+                mut_scale=self.mut_scale, seed=self.seed, gen=self.gen)
+            if self.use_gpu:
+                from ..ops.ga import ga_evolve_family_gpu
+                self.pop_t = ga_evolve_family_gpu(
+                    self.pop_t, fitness, self.bounds_t, **kw)
+            else:
+                from ..ops.ga import ga_evolve_family_cpu
+                child = ga_evolve_family_cpu(
+                    self.pop_t.cpu().numpy(), fitness.cpu().numpy(),
+                    self.fam.bounds, self.fam.clip, **kw)
+                self.pop_t = torch.from_numpy(child).to(self.device)
+        elif self.use_gpu:
             from ..ops.ga import ga_evolve_gpu
             self.pop_t = ga_evolve_gpu(
                 self.pop_t, fitness,

@@ -21,6 +21,8 @@ SO_PATH = OPS_DIR / "_hip_ops.so"
 SOURCES = [
     "backtest.hip",
     "backtest_tp.hip",
+    "backtest_grid.hip",
+    "backtest_dca.hip",
     "ga.hip",
     "montecarlo.hip",
     "covar.hip",
@@ -60,7 +62,7 @@ def _compile_flags() -> list[str]:
 
 def build(verbose: bool = True, force: bool = False) -> Path:
     BUILD_DIR.mkdir(exist_ok=True)
-    common_hpp = HIP_DIR / "common.hpp"
+    hdr_mtime = max(h.stat().st_mtime for h in HIP_DIR.glob("*.hpp"))
     objs = []
     relink = force or not SO_PATH.exists()
     for src_name in SOURCES:
@@ -69,7 +71,7 @@ def build(verbose: bool = True, force: bool = False) -> Path:
             continue
         obj = BUILD_DIR / (src_name + ".o")
         objs.append(obj)
-        deps_mtime = max(src.stat().st_mtime, common_hpp.stat().st_mtime)
+        deps_mtime = max(src.stat().st_mtime, hdr_mtime)
         if not force and obj.exists() and obj.stat().st_mtime > deps_mtime:
             continue
         cmd = [HIPCC, *_compile_flags(), "-c", str(src), "-o", str(obj)]

@@ -28,6 +28,15 @@ extern "C" void launch_ga_evolve(const float*, const float*, const int*,
                                  const float*, float*, int, int, int, float,
                                  float, float, uint64_t, uint64_t,
                                  hipStream_t);
+extern "C" void launch_backtest_grid(const float*, const float*, float*, int,
+                                     int, int, float, hipStream_t);
+extern "C" void launch_backtest_dca(const float*, const float*, float*, int,
+                                    int, int, float, hipStream_t);
+extern "C" void launch_ga_evolve_generic(const float*, const float*,
+                                         const int*, const float*, float*,
+                                         int, int, int, int, float, float,
+                                         float, uint64_t, uint64_t,
+                                         hipStream_t);
 extern "C" void launch_mc_paths(const float*, const float*, const float*,
                                 const float*, float*, float*, int, int, long,
                                 float, uint64_t, long, int, hipStream_t);
@@ -153,6 +162,51 @@ PYBIND11_MODULE(_hip_ops, m) {
                                tournament, cx_rate, mut_rate, mut_scale, seed,
                                gen, as_stream(stream));
               check(hipGetLastError(), "ga_evolve launch");
+          });
+
+    // strategy families (backtest_grid.hip / backtest_dca.hip): same
+    // argument shape as `backtest`
+    m.def("backtest_grid",
+          [](uintptr_t candles, uintptr_t pop, uintptr_t metrics, int nsym,
+             int T, int P, float initial_equity, uintptr_t stream) {
+              launch_backtest_grid(reinterpret_cast<const float*>(candles),
+                                   reinterpret_cast<const float*>(pop),
+                                   reinterpret_cast<float*>(metrics), nsym,
+                                   T, P, initial_equity, as_stream(stream));
+              check(hipGetLastError(), "backtest_grid launch");
+          },
+          py::arg("candles"), py::arg("pop"), py::arg("metrics"),
+          py::arg("nsym"), py::arg("T"), py::arg("P"),
+          py::arg("initial_equity"), py::arg("stream"));
+
+    m.def("backtest_dca",
+          [](uintptr_t candles, uintptr_t pop, uintptr_t metrics, int nsym,
+             int T, int P, float initial_equity, uintptr_t stream) {
+              launch_backtest_dca(reinterpret_cast<const float*>(candles),
+                                  reinterpret_cast<const float*>(pop),
+                                  reinterpret_cast<float*>(metrics), nsym,
+                                  T, P, initial_equity, as_stream(stream));
+              check(hipGetLastError(), "backtest_dca launch");
+          },
+          py::arg("candles"), py::arg("pop"), py::arg("metrics"),
+          py::arg("nsym"), py::arg("T"), py::arg("P"),
+          py::arg("initial_equity"), py::arg("stream"));
+
+    m.def("ga_evolve_generic",
+          [](uintptr_t pop, uintptr_t fitness, uintptr_t order,
+             uintptr_t bounds, uintptr_t out, int P, int nparam,
+             int elite_k, int tournament, float cx_rate, float mut_rate,
+             float mut_scale, uint64_t seed, uint64_t gen,
+             uintptr_t stream) {
+              launch_ga_evolve_generic(
+                  reinterpret_cast<const float*>(pop),
+                  reinterpret_cast<const float*>(fitness),
+                  reinterpret_cast<const int*>(order),
+                  reinterpret_cast<const float*>(bounds),
+                  reinterpret_cast<float*>(out), P, nparam, elite_k,
+                  tournament, cx_rate, mut_rate, mut_scale, seed, gen,
+                  as_stream(stream));
+              check(hipGetLastError(), "ga_evolve_generic launch");
           });
 
     m.def("mc_paths",

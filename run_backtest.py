@@ -8,6 +8,8 @@ Examples:
   python run_backtest.py backtest --symbol BTCUSDC --strategy dca_strategy
   python run_backtest.py backtest --symbol BTCUSDC --strategy momentum --plot
   python run_backtest.py optimize --symbol BTCUSDC --pop 256 --generations 10
+  python run_backtest.py optimize --symbol BTCUSDC --strategy grid
+  python run_backtest.py backtest --symbol BTCUSDC --strategy dca
   python run_backtest.py list
   python run_backtest.py analyze [--metric sharpe_ratio]
 """
@@ -23,6 +25,7 @@ from ai_crypto_trader_amd.backtesting.data_manager import (
 from ai_crypto_trader_amd.backtesting.engine import (
     STRATEGY_PRESETS, BacktestEngine,
 )
+from ai_crypto_trader_amd.backtesting.families import FAMILIES
 from ai_crypto_trader_amd.backtesting.result_analyzer import ResultAnalyzer
 
 
@@ -40,7 +43,9 @@ def main():
     b = sub.add_parser("backtest", help="run a backtest")
     b.add_argument("--symbol", required=True)
     b.add_argument("--strategy", default="default",
-                   choices=sorted(STRATEGY_PRESETS))
+                   choices=sorted([*STRATEGY_PRESETS, *FAMILIES]),
+                   help="a vote-machine preset, or the strategy family "
+                        "grid / dca")
     b.add_argument("--interval", default="1m")
     b.add_argument("--candles", type=int, default=10_000)
     b.add_argument("--cpu", action="store_true",
@@ -55,6 +60,10 @@ def main():
     o.add_argument("--generations", type=int, default=10)
     o.add_argument("--candles", type=int, default=20_000)
     o.add_argument("--cpu", action="store_true")
+    o.add_argument("--strategy", default="vote",
+                   choices=["vote", *sorted(FAMILIES)],
+                   help="parameter space to search: the vote machine or "
+                        "the grid / dca strategy family")
 
     sub.add_parser("list", help="list stored data and results")
     an = sub.add_parser("analyze",
@@ -97,7 +106,7 @@ def main():
         eng = BacktestEngine(args.data_dir,
                              device="cpu" if args.cpu else None)
         stats = eng.optimize(args.symbol, args.pop, args.generations,
-                             args.candles)
+                             args.candles, strategy=args.strategy)
         print(json.dumps(stats, indent=2, default=str))
         return
 

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Per-kernel microbenchmarks (GPU): backtest, Monte-Carlo, covariance,
+"""Per-kernel microbenchmarks (GPU): backtest (vote, grid, DCA), Monte-Carlo, covariance,
 indicators, LSTM fwd/bwd, GA evolve, env step, GAE.
 
 Used for rocprofv3 runs and optimization A/Bs:
@@ -61,6 +61,36 @@ def bench_backtest(reps):
     return {"kernel": "backtest", "ms": dt * 1e3,
             "candles_per_sec": P * nsym * T / dt,
             "config": {"nsym": nsym, "T": T, "P": P}}
+
+
+def _bench_family(name, reps):
+    """Strategy-family kernel at bench_backtest's shape (same market, same
+    P), so the row reads directly against the vote `backtest` row."""
+    from ai_crypto_trader_amd.backtesting.families import FAMILIES
+    from ai_crypto_trader_amd.data.synthetic import (
+        candles_chl_v, generate_ohlcv,
+    )
+
+    fam = FAMILIES[name]
+    nsym, T, P = 64, 1_000_000, 1024
+    candles = torch.from_numpy(
+        candles_chl_v(generate_ohlcv(T, nsym, seed=0))).cuda()
+    pop = torch.from_numpy(fam.random_population(P, seed=1)).cuda()
+    dt = timed(lambda: fam.run_gpu(candles, pop), reps)
+    m = fam.run_gpu(candles, pop)
+    torch.cuda.synchronize()
+    return {"kernel": f"backtest_{name}", "ms": dt * 1e3,
+            "candles_per_sec": P * nsym * T / dt,
+            "trades_per_lane": float(m[..., 1].mean()),
+            "config": {"nsym": nsym, "T": T, "P": P}}
+
+
+def bench_backtest_grid(reps):
+    return _bench_family("grid", reps)
+
+
+def bench_backtest_dca(reps):
+    return _bench_family("dca", reps)
 
 
 def bench_mc(reps):
@@ -228,7 +258,8 @@ def bench_gae(reps):
 
 
 BENCHES = {
-    "backtest": bench_backtest, "mc": bench_mc, "mc_bootstrap": bench_mc_bootstrap, "cov": bench_cov,
+    "backtest": bench_backtest, "backtest_grid": bench_backtest_grid,
+    "backtest_dca": bench_backtest_dca, "mc": bench_mc, "mc_bootstrap": bench_mc_bootstrap, "cov": bench_cov,
     "indicators": bench_indicators, "lstm": bench_lstm, "gru": bench_gru, "env": bench_env,
     "gae": bench_gae, "attn": bench_attn,
 }
