@@ -11,7 +11,8 @@ lanes.
 
 A strategy is a flat float32 vector with the layout below. The same layout
 is consumed by the numpy reference engine (backtesting/engine_cpu.py) and
-the HIP backtest kernel (ops/hip/backtest.hip) — keep the three in sync.
+the HIP backtest kernels (ops/hip/bt_vote.hpp holds their one copy of this
+contract) — keep the three in sync.
 
 Param vector layout (NPARAM float32 slots):
   0  rsi_period        Wilder RSI period            [2, 64]   (rounded to int)

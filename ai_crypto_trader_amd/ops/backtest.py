@@ -11,7 +11,9 @@ import torch
 
 from . import require_hip_ops
 from ..backtesting.engine_cpu import NMETRIC
-from ..backtesting.strategy import NPARAM
+from ..backtesting.strategy import (
+    MAX_WIN, NPARAM, RESNAP, SHARED_HALO, WARMUP,
+)
 
 
 def run_backtest_gpu(
@@ -53,8 +55,6 @@ def pick_nshards(nsym: int, T: int, P: int, *, target_blocks: int = 6144,
     warm tail. 24 shards x 8 even time groups measured best end-to-end
     at the flagship shape (234 G/s; full sweep in
     profiles/backtest_continuous_pmc.json)."""
-    from ..backtesting.strategy import RESNAP
-
     chunks = (P + 255) // 256
     base = nsym * chunks
     want = max(1, -(-target_blocks // base))
@@ -63,6 +63,21 @@ def pick_nshards(nsym: int, T: int, P: int, *, target_blocks: int = 6144,
 
 
 _pipe_streams: dict = {}
+
+_contract_checked = False
+
+
+def _check_contract(ops) -> None:
+    """The constants compiled into the kernels (ops/hip/bt_vote.hpp) must
+    be the ones backtesting/strategy.py specifies. Checked once."""
+    global _contract_checked
+    if _contract_checked:
+        return
+    got = (ops.BT_NPARAM, ops.BT_NMETRIC, ops.BT_MAXWIN, ops.BT_HALO,
+           ops.BT_WARMUP, ops.BT_RESNAP)
+    want = (NPARAM, NMETRIC, MAX_WIN, SHARED_HALO, WARMUP, RESNAP)
+    assert got == want, f"kernel contract {got} != strategy.py {want}"
+    _contract_checked = True
 
 
 def run_backtest_continuous_gpu(
@@ -93,6 +108,7 @@ def run_backtest_continuous_gpu(
     independent of lane count, so symbol groups serialize G full-length
     chains.)"""
     ops = require_hip_ops()
+    _check_contract(ops)
     assert candles.is_cuda and population.is_cuda
     assert candles.dtype == torch.float32
     assert population.dtype == torch.float32
@@ -101,8 +117,6 @@ def run_backtest_continuous_gpu(
     population = population.contiguous()
     nsym, T, _ = candles.shape
     P = population.shape[0]
-    from ..backtesting.strategy import RESNAP
-
     if nshards <= 0:
         nshards = pick_nshards(nsym, T, P, tail=tail)
     # shard bodies must be RESNAP-aligned (BB restart exactness)
@@ -115,8 +129,8 @@ def run_backtest_continuous_gpu(
         eflags = torch.empty((nsym, nwords, P), dtype=torch.int64,
                              device=dev)
         xflags = torch.empty_like(eflags)
-        carry = torch.empty((P, nsym, 18), dtype=torch.float32,
-                            device=dev)
+        carry = torch.empty((P, nsym, ops.BT_NSTATE),
+                            dtype=torch.float32, device=dev)
         _flag_cache.clear()      # one shape live at a time (16 GB-class)
         _flag_cache[key] = (eflags, xflags, carry)
     else:

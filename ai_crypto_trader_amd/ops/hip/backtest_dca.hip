@@ -27,17 +27,17 @@
 // spills, 6,656 B LDS/block, occupancy 8 waves/SIMD. Measured rates:
 // docs/KERNELS.md "Strategy families".
 
-#include "bt_metrics.hpp"
+#include "bt_common.hpp"
 
 #define DC_NPARAM 7
 #define DC_LOOKBACK 120          // == strategy_dca.py DIP_LOOKBACK
 #define DC_HALO 128              // >= DC_LOOKBACK - 1
-#define DC_SPAN (FAM_TILE + DC_HALO)
+#define DC_SPAN (BT_TILE + DC_HALO)
 #define DC_NEVER (-(1 << 20))    // == strategy_dca.py NEVER
 
 namespace {
 
-__global__ void __launch_bounds__(FAM_BLOCK) backtest_dca_kernel(
+__global__ void __launch_bounds__(BT_BLOCK) backtest_dca_kernel(
     const float* __restrict__ candles,   // (nsym, T, 4)
     const float* __restrict__ pop,       // (P, DC_NPARAM)
     float* __restrict__ metrics,         // (P, nsym, NMETRIC)
@@ -45,17 +45,17 @@ __global__ void __launch_bounds__(FAM_BLOCK) backtest_dca_kernel(
 {
 #pragma clang fp contract(off)           // match the numpy f32 reference
     __shared__ float chist[DC_SPAN];     // close history incl. halo
-    __shared__ float shigh[FAM_TILE];
-    __shared__ float4 tile[FAM_TILE];    // close, high, rmax120, -
+    __shared__ float shigh[BT_TILE];
+    __shared__ float4 tile[BT_TILE];    // close, high, rmax120, -
 
     int sym, chunk;
-    fam_block_map(blockIdx.x, nsym, chunks_per_sym, sym, chunk);
+    bt_block_map(blockIdx.x, nsym, chunks_per_sym, sym, chunk);
     const int tid = threadIdx.x;
-    const int p = chunk * FAM_BLOCK + tid;
+    const int p = chunk * BT_BLOCK + tid;
     const bool act = p < P;
     const float* pr = pop + (long)(act ? p : 0) * DC_NPARAM;
 
-    const float omf = 1.0f - FAM_FEE;
+    const float omf = 1.0f - BT_FEE;
     const int period = max((int)pr[0], 1);
     const float base = pr[1] * initial_equity;
     const float four_base = 4.0f * base;
@@ -68,17 +68,17 @@ __global__ void __launch_bounds__(FAM_BLOCK) backtest_dca_kernel(
     float cash = initial_equity, units = 0.f, invested = 0.f;
     float tp_price = 0.f;
     int since = 0, nper = 0, last_dip = DC_NEVER;
-    FamAccum acc;
+    BtAccum acc;
     acc.init(initial_equity);
 
     const float4* sym_candles =
         reinterpret_cast<const float4*>(candles + (long)sym * T * 4);
 
-    for (int t0 = 0; t0 < T; t0 += FAM_TILE) {
-        const int tend = min(FAM_TILE, T - t0);
+    for (int t0 = 0; t0 < T; t0 += BT_TILE) {
+        const int tend = min(BT_TILE, T - t0);
         __syncthreads();
         // stage [t0 - HALO, t0 + TILE); -inf left of t=0 (max identity)
-        for (int i = tid; i < DC_SPAN; i += FAM_BLOCK) {
+        for (int i = tid; i < DC_SPAN; i += BT_BLOCK) {
             const int t = t0 - DC_HALO + i;
             float cl = -INFINITY, hi = 0.0f;
             if (t >= 0 && t < T) {
@@ -139,7 +139,7 @@ __global__ void __launch_bounds__(FAM_BLOCK) backtest_dca_kernel(
     }
 
     if (act)
-        acc.finalize(metrics + ((long)p * nsym + sym) * FAM_NMETRIC, T);
+        acc.finalize(metrics + ((long)p * nsym + sym) * BT_NMETRIC, T);
 }
 
 }  // namespace
@@ -148,8 +148,8 @@ extern "C" void launch_backtest_dca(const float* candles, const float* pop,
                                     float* metrics, int nsym, int T, int P,
                                     float initial_equity,
                                     hipStream_t stream) {
-    const int chunks = (P + FAM_BLOCK - 1) / FAM_BLOCK;
+    const int chunks = (P + BT_BLOCK - 1) / BT_BLOCK;
     hipLaunchKernelGGL(backtest_dca_kernel, dim3(nsym * chunks),
-                       dim3(FAM_BLOCK), 0, stream, candles, pop, metrics,
+                       dim3(BT_BLOCK), 0, stream, candles, pop, metrics,
                        nsym, T, P, chunks, initial_equity);
 }

@@ -40,7 +40,7 @@
 // the arithmetic above predicts. Measured rates and what bounds them:
 // docs/KERNELS.md "Strategy families".
 
-#include "bt_metrics.hpp"
+#include "bt_common.hpp"
 
 #define GR_NPARAM 5
 #define GR_MAXHALF 16            // == strategy_grid.py MAX_HALF
@@ -60,7 +60,7 @@ struct GridLane {
     float sell_px, buy_px, up_thr, dn_thr;
     float cash;
     double units_total;
-    FamAccum acc;
+    BtAccum acc;
 
     __device__ void load(const float* __restrict__ pr, float initial_equity)
     {
@@ -82,7 +82,7 @@ struct GridLane {
     }
 
     // units held by filled slot k
-    __device__ float slot_units(const float (*lev)[FAM_BLOCK], int tid,
+    __device__ float slot_units(const float (*lev)[BT_BLOCK], int tid,
                                 int k) const
     {
 #pragma clang fp contract(off)
@@ -90,17 +90,17 @@ struct GridLane {
     }
 
     // reload the two cursor levels from the table
-    __device__ void refresh_px(const float (*lev)[FAM_BLOCK], int tid)
+    __device__ void refresh_px(const float (*lev)[BT_BLOCK], int tid)
     {
         const uint32_t empt = ~filled & slotmask;
         sell_px = filled ? lev[__ffs((int)filled)][tid] : INFINITY;
         buy_px = empt ? lev[31 - __clz((int)empt)][tid] : -INFINITY;
     }
 
-    __device__ void build(float (*lev)[FAM_BLOCK], int tid, float close)
+    __device__ void build(float (*lev)[BT_BLOCK], int tid, float close)
     {
 #pragma clang fp contract(off)
-        const float omf = 1.0f - FAM_FEE;
+        const float omf = 1.0f - BT_FEE;
         b = cf * cash / (float)twoH;
         bomf = b * omf;
         u0 = bomf / close;
@@ -132,11 +132,11 @@ struct GridLane {
         refresh_px(lev, tid);
     }
 
-    __device__ void step(float (*lev)[FAM_BLOCK], int tid, float close,
+    __device__ void step(float (*lev)[BT_BLOCK], int tid, float close,
                          float high, float low)
     {
 #pragma clang fp contract(off)
-        const float omf = 1.0f - FAM_FEE;
+        const float omf = 1.0f - BT_FEE;
         const uint32_t f0 = filled;          // pre-candle fill state
         bool touched = false;
         // --- 1. sells, ascending k ---------------------------------------
@@ -190,20 +190,20 @@ struct GridLane {
 };
 
 // min 4 blocks/CU: what the LDS footprint allows (see header)
-__global__ void __launch_bounds__(FAM_BLOCK, 4) backtest_grid_kernel(
+__global__ void __launch_bounds__(BT_BLOCK, 4) backtest_grid_kernel(
     const float* __restrict__ candles,   // (nsym, T, 4)
     const float* __restrict__ pop,       // (P, GR_NPARAM)
     float* __restrict__ metrics,         // (P, nsym, NMETRIC)
     int nsym, int T, int P, int chunks_per_sym, float initial_equity)
 {
 #pragma clang fp contract(off)
-    __shared__ float lev[GR_NLEV][FAM_BLOCK];   // [level][lane]
-    __shared__ float4 tile[FAM_TILE];           // close, high, low, volume
+    __shared__ float lev[GR_NLEV][BT_BLOCK];   // [level][lane]
+    __shared__ float4 tile[BT_TILE];           // close, high, low, volume
 
     int sym, chunk;
-    fam_block_map(blockIdx.x, nsym, chunks_per_sym, sym, chunk);
+    bt_block_map(blockIdx.x, nsym, chunks_per_sym, sym, chunk);
     const int tid = threadIdx.x;
-    const int p = chunk * FAM_BLOCK + tid;
+    const int p = chunk * BT_BLOCK + tid;
     const bool act = p < P;
 
     GridLane st;
@@ -212,8 +212,8 @@ __global__ void __launch_bounds__(FAM_BLOCK, 4) backtest_grid_kernel(
     const float4* sym_candles =
         reinterpret_cast<const float4*>(candles + (long)sym * T * 4);
 
-    for (int t0 = 0; t0 < T; t0 += FAM_TILE) {
-        const int tend = min(FAM_TILE, T - t0);
+    for (int t0 = 0; t0 < T; t0 += BT_TILE) {
+        const int tend = min(BT_TILE, T - t0);
         __syncthreads();
         if (tid < tend) tile[tid] = sym_candles[t0 + tid];
         __syncthreads();
@@ -227,7 +227,7 @@ __global__ void __launch_bounds__(FAM_BLOCK, 4) backtest_grid_kernel(
     }
 
     if (act)
-        st.acc.finalize(metrics + ((long)p * nsym + sym) * FAM_NMETRIC, T);
+        st.acc.finalize(metrics + ((long)p * nsym + sym) * BT_NMETRIC, T);
 }
 
 }  // namespace
@@ -236,8 +236,8 @@ extern "C" void launch_backtest_grid(const float* candles, const float* pop,
                                      float* metrics, int nsym, int T, int P,
                                      float initial_equity,
                                      hipStream_t stream) {
-    const int chunks = (P + FAM_BLOCK - 1) / FAM_BLOCK;
+    const int chunks = (P + BT_BLOCK - 1) / BT_BLOCK;
     hipLaunchKernelGGL(backtest_grid_kernel, dim3(nsym * chunks),
-                       dim3(FAM_BLOCK), 0, stream, candles, pop, metrics,
+                       dim3(BT_BLOCK), 0, stream, candles, pop, metrics,
                        nsym, T, P, chunks, initial_equity);
 }

@@ -44,154 +44,15 @@
 // Reference semantics: backtesting/strategy.py (shared CPU/GPU
 // contract); replaces the per-candle loop of the reference's
 // backtesting/strategy_tester.py:190-300 at continuous (multi-year
-// single-history) shape.
+// single-history) shape. Phase 1 is bt_vote.hpp's VoteState — the very
+// indicator/vote code backtest.hip marches — over the shared tile
+// staging; the metrics formula and block map are bt_common.hpp.
 
-#include "common.hpp"
+#include "bt_vote.hpp"
 
-#define BT_BLOCK 256
-#define BT_TILE 256
-#define BT_MAXWIN 32
-#define BT_HALO 64
-#define BT_SPAN (BT_TILE + BT_HALO)
-#define BT_NPARAM 19
-#define BT_NMETRIC 10
-#define BT_WARMUP 128
-#define BT_RESNAP 16384
-#define BT_FEE 0.001f
-#define BT_EPS 1e-9f
-// float32(sqrt(525600)) EXACTLY (0x44353ee6) — see backtest.hip
-#define BT_ANNUALIZE 0x1.6a7dccp+9f
+#define BT_TBLOCK 512            // bt_trades_kernel: producer + consumer
 
 namespace {
-
-// ---------------------------------------------------------------------
-// Phase 1: indicator/vote state (no position, no metrics)
-// ---------------------------------------------------------------------
-struct FlagState {
-    float inv_rsi_p, rsi_os, rsi_ob;
-    float a_f, a_s, a_sig;
-    int bb_w;
-    float bb_k, bb_bth, bb_sth;
-    int entry_v, exit_v;
-    float stoch_os, stoch_ob, will_os, will_ob;
-
-    float ema_f, ema_s, sig;
-    float avg_gain, avg_loss;
-    double bb_sum, bb_sum2, inv_w;
-
-    __device__ void load(const float* __restrict__ pr)
-    {
-        inv_rsi_p = 1.0f / fmaxf(floorf(pr[0]), 1.0f);
-        rsi_os = pr[1]; rsi_ob = pr[2];
-        a_f = 2.0f / (pr[3] + 1.0f);
-        a_s = 2.0f / (pr[4] + 1.0f);
-        a_sig = 2.0f / (pr[5] + 1.0f);
-        bb_w = min(max((int)pr[6], 2), BT_MAXWIN);
-        bb_k = pr[7]; bb_bth = pr[8]; bb_sth = pr[9];
-        entry_v = (int)pr[10]; exit_v = (int)pr[11];
-        stoch_os = pr[17]; stoch_ob = pr[18];
-        will_os = stoch_os - 100.0f;
-        will_ob = stoch_ob - 100.0f;
-        ema_f = ema_s = sig = 0.f;
-        avg_gain = avg_loss = 0.f;
-        bb_sum = bb_sum2 = 0.0;
-        inv_w = 1.0 / (double)bb_w;
-    }
-
-    // warm-tail march: the same f32 recurrence ops as step(), minus
-    // Bollinger (resnapped at body start) and votes
-    __device__ void warm_step(float close, float change)
-    {
-#pragma clang fp contract(off)
-        ema_f += a_f * (close - ema_f);
-        ema_s += a_s * (close - ema_s);
-        float macd = ema_f - ema_s;
-        sig += a_sig * (macd - sig);
-        float gain = fmaxf(change, 0.0f);
-        float loss = fmaxf(-change, 0.0f);
-        avg_gain += (gain - avg_gain) * inv_rsi_p;
-        avg_loss += (loss - avg_loss) * inv_rsi_p;
-    }
-
-    __device__ void resnap(const float* __restrict__ hist)
-    {
-#pragma clang fp contract(off)
-        double s = 0.0, s2 = 0.0;
-        const int w = bb_w;
-        for (int j = BT_MAXWIN - 1; j >= 0; --j) {
-            if (j < w) {
-                double c = (double)hist[-j];
-                s += c;
-                s2 += c * c;
-            }
-        }
-        bb_sum = s;
-        bb_sum2 = s2;
-    }
-
-    // Full body candle: indicators + votes -> (entry, exit) bits.
-    // SKIP_BB is compile-time (resnap peeled at the call site) so the
-    // steady-state loop carries no per-candle branch.
-    template <bool SKIP_BB>
-    __device__ uint2 candle(int t, float close, float change,
-                            float oldc, double csq_new, double csq_old,
-                            float4 sv)
-    {
-#pragma clang fp contract(off)
-        if (t == 0) { ema_f = close; ema_s = close; }
-        else {
-            ema_f += a_f * (close - ema_f);
-            ema_s += a_s * (close - ema_s);
-        }
-        float macd = ema_f - ema_s;
-        sig += a_sig * (macd - sig);
-        float macd_hist = macd - sig;
-
-        float gain = fmaxf(change, 0.0f);
-        float loss = fmaxf(-change, 0.0f);
-        avg_gain += (gain - avg_gain) * inv_rsi_p;
-        avg_loss += (loss - avg_loss) * inv_rsi_p;
-        float rsi_num = 100.0f * avg_gain;
-        float rsi_den = avg_gain + fmaxf(avg_loss, BT_EPS);
-
-        if (!SKIP_BB) {
-            double old = (double)oldc;
-            double c64 = (double)close;
-            bb_sum += c64 - old;
-            bb_sum2 += csq_new - csq_old;
-        }
-        double inv_cnt = inv_w;
-        // the early-window divisor only exists in the very first tile
-        // (t < MAX_WIN <= 32 < BT_TILE)
-        if (t < BT_MAXWIN && t + 1 < bb_w)
-            inv_cnt = 1.0 / (t + 1.0);
-        double mean64 = bb_sum * inv_cnt;
-        double var64 = fmax(bb_sum2 * inv_cnt - mean64 * mean64, 0.0);
-        float mean = (float)mean64;
-        float std_ = sqrtf((float)var64);
-        float band = bb_k * std_;
-        float bb_num = close - (mean - band);
-        float bb_den = fmaxf(2.0f * band, BT_EPS);
-
-        int net = 0;
-        if (t >= BT_WARMUP) {
-            int buy = (rsi_num < rsi_os * rsi_den) +
-                      (macd_hist > 0.0f) +
-                      (bb_num < bb_bth * bb_den) +
-                      (sv.x < stoch_os * sv.z) +
-                      (sv.y < will_os * sv.z) +
-                      (sv.w > 0.0f);
-            int sell = (rsi_num > rsi_ob * rsi_den) +
-                       (macd_hist < 0.0f) +
-                       (bb_num > bb_sth * bb_den) +
-                       (sv.x > stoch_ob * sv.z) +
-                       (sv.y > will_ob * sv.z) +
-                       (sv.w < 0.0f);
-            net = buy - sell;
-        }
-        return make_uint2(net >= entry_v, net <= -exit_v);
-    }
-};
 
 // ---------------------------------------------------------------------
 // Phase 2: position machine + metrics (exact engine_cpu op order).
@@ -203,7 +64,11 @@ struct FlagState {
 // block, whose division would otherwise be a third serial IEEE-divide
 // per candle. The two mark divisions (r and drawdown) only feed
 // accumulators, never the trading state, so with a branchless body the
-// scheduler pipelines them across unrolled iterations.
+// scheduler pipelines them across unrolled iterations. That is why this
+// is deliberately NOT backtest.hip's branchy BtState position machine
+// (which sits behind a long indicator chain at 5 waves/SIMD, where exec-
+// masked branches are the cheaper form): same contract, same bits,
+// different shape — keep the two apart.
 // ---------------------------------------------------------------------
 struct TradeState {
     float size_pct;
@@ -345,7 +210,7 @@ __global__ void __launch_bounds__(BT_BLOCK) bt_flags_kernel(
     const bool act = p < P;
     const long nwords = (T + 63) >> 6;
 
-    FlagState st;
+    VoteState st;                    // indicators + votes only
     st.load(pop + (long)(act ? p : 0) * BT_NPARAM);
 
     // balanced RESNAP-aligned shard boundaries: floor(s*T/S) to the
@@ -376,23 +241,7 @@ __global__ void __launch_bounds__(BT_BLOCK) bt_flags_kernel(
     unsigned long long ew = 0ull, xw = 0ull;
 
     for (int t0 = start; t0 < hi; t0 += BT_TILE) {
-        __syncthreads();
-        for (int i = tid; i < BT_SPAN; i += BT_BLOCK) {
-            const int t = t0 - BT_HALO + i;
-            if (t >= 0 && t < T) {
-                float4 c = sym_candles[t];
-                chist[i] = c.x;
-                csq[i] = (double)c.x * (double)c.x;
-                hl[i][0] = c.y;
-                hl[i][1] = c.z;
-            } else {
-                chist[i] = 0.0f;
-                csq[i] = 0.0;
-                hl[i][0] = 0.0f;
-                hl[i][1] = 0.0f;
-            }
-        }
-        __syncthreads();
+        bt_stage_tile(sym_candles, t0, T, chist, hl, csq);
         const int tend = min(BT_TILE, hi - t0);
 
         if (t0 < lo) {
@@ -410,31 +259,7 @@ __global__ void __launch_bounds__(BT_BLOCK) bt_flags_kernel(
         }
 
         // body tile: shared vote series (exact, finite-window)
-        if (tid < tend) {
-            const int t = t0 + tid;
-            const int base = tid + BT_HALO;
-            const float cl = chist[base];
-            const int L14 = min(t + 1, 14);
-            float hmax = -1e30f, lmin = 1e30f;
-            for (int j = 0; j < L14; ++j) {
-                hmax = fmaxf(hmax, hl[base - j][0]);
-                lmin = fminf(lmin, hl[base - j][1]);
-            }
-            const int L20 = min(t + 1, 20);
-            double s20 = 0.0;
-            for (int j = 0; j < L20; ++j) s20 += (double)chist[base - j];
-            const float sma20 = (float)(s20 / (double)L20);
-            const int L50 = min(t + 1, 50);
-            double s50 = 0.0;
-            for (int j = 0; j < L50; ++j) s50 += (double)chist[base - j];
-            const float sma50 = (float)(s50 / (double)L50);
-            const float trend = (cl > sma20 && sma20 > sma50) ? 1.0f
-                                : ((cl < sma20 && sma20 < sma50) ? -1.0f
-                                                                 : 0.0f);
-            sh_vote[tid] = make_float4(
-                100.0f * (cl - lmin), -100.0f * (hmax - cl),
-                fmaxf(hmax - lmin, BT_EPS), trend);
-        }
+        bt_shared_votes(t0, tend, chist, hl, sh_vote);
         __syncthreads();
 
         // BB resnap at RESNAP-aligned tiles (all shards see the same
@@ -445,12 +270,12 @@ __global__ void __launch_bounds__(BT_BLOCK) bt_flags_kernel(
             st.resnap(&chist[BT_HALO]);
             // peeled resnap candle (compile-time SKIP_BB)
             const float close = chist[BT_HALO];
-            uint2 b = st.candle<true>(
+            const int net = st.step<true>(
                 t0, close, close - prev_close,
                 chist[BT_HALO - st.bb_w], csq[BT_HALO],
                 csq[BT_HALO - st.bb_w], sh_vote[0]);
-            ew |= (unsigned long long)b.x << (t0 & 63);
-            xw |= (unsigned long long)b.y << (t0 & 63);
+            ew |= (unsigned long long)(net >= st.entry_v) << (t0 & 63);
+            xw |= (unsigned long long)(net <= -st.exit_v) << (t0 & 63);
             prev_close = close;
             tt0 = 1;
         }
@@ -458,13 +283,13 @@ __global__ void __launch_bounds__(BT_BLOCK) bt_flags_kernel(
             const int t = t0 + tt;
             const float close = chist[tt + BT_HALO];
             const float change = (t == 0) ? 0.0f : close - prev_close;
-            uint2 b = st.candle<false>(
+            const int net = st.step<false>(
                 t, close, change, chist[tt + BT_HALO - st.bb_w],
                 csq[tt + BT_HALO], csq[tt + BT_HALO - st.bb_w],
                 sh_vote[tt]);
             const int bit = t & 63;
-            ew |= (unsigned long long)b.x << bit;
-            xw |= (unsigned long long)b.y << bit;
+            ew |= (unsigned long long)(net >= st.entry_v) << bit;
+            xw |= (unsigned long long)(net <= -st.exit_v) << bit;
             if (bit == 63 || t == T - 1) {
                 if (act) {
                     const long w = t >> 6;
@@ -481,7 +306,7 @@ __global__ void __launch_bounds__(BT_BLOCK) bt_flags_kernel(
 
 // ---------------------------------------------------------------------
 // Kernel 2: trades. Grid = nsym x chunks blocks of 512 threads
-// (XCD-affine mapping as in backtest.hip).
+// (XCD-affine bt_block_map).
 //
 // Producer-consumer split: waves 0-3 (tid 0-255, one lane per param)
 // run the position state machine; waves 4-7 (tid 256-511, same params
@@ -495,10 +320,8 @@ __global__ void __launch_bounds__(BT_BLOCK) bt_flags_kernel(
 // engine_cpu (the consumer reads the exact f32 equity values the
 // producer assigned).
 // ---------------------------------------------------------------------
-// dynamic TradeState slots persisted between chunked launches:
-// producer owns [0..12], consumer owns [13..16]
-#define BT_NSTATE 18
-#define BT_TBLOCK 512
+// BT_NSTATE (bt_vote.hpp) floats per lane persist between chunked
+// launches: producer owns [0..12], consumer owns [13..16]
 
 __global__ void __launch_bounds__(BT_TBLOCK) bt_trades_kernel(
     const float* __restrict__ candles,       // offset to symbol group
@@ -520,17 +343,8 @@ __global__ void __launch_bounds__(BT_TBLOCK) bt_trades_kernel(
     __shared__ float eqbuf[2][32][256];
     __shared__ int skipw[2][4];              // per-producer-wave skip
 
-    int bid = blockIdx.x;
     int sym, chunk;
-    int nblocks = nsym * chunks_per_sym;
-    if ((nsym & 7) == 0 && (nblocks & 7) == 0) {
-        int xcd = bid & 7, j = bid >> 3;
-        sym = xcd + 8 * (j / chunks_per_sym);
-        chunk = j % chunks_per_sym;
-    } else {
-        sym = bid / chunks_per_sym;
-        chunk = bid % chunks_per_sym;
-    }
+    bt_block_map(blockIdx.x, nsym, chunks_per_sym, sym, chunk);
     const int tid = threadIdx.x;
     const bool is_prod = tid < 256;
     const int lane = tid & 255;
@@ -658,8 +472,7 @@ __global__ void __launch_bounds__(BT_TBLOCK) bt_trades_kernel(
     }
 
     // finalize: producer publishes its five trade metrics through LDS;
-    // the consumer computes sharpe/fitness and writes all ten
-    // (identical formulas to backtest.hip BtState::finalize)
+    // the consumer, which holds the other four, writes all ten
     if (is_prod) {
         eqbuf[0][0][lane] = st.equity;
         eqbuf[0][1][lane] = st.n_trades;
@@ -668,29 +481,12 @@ __global__ void __launch_bounds__(BT_TBLOCK) bt_trades_kernel(
         eqbuf[0][4][lane] = st.gross_l;
     }
     __syncthreads();
-    if (!is_prod && act) {
-        float equity = eqbuf[0][0][lane];
-        float n_trades = eqbuf[0][1][lane];
-        float wins = eqbuf[0][2][lane];
-        float gross_p = eqbuf[0][3][lane];
-        float gross_l = eqbuf[0][4][lane];
-        float n = (float)max(T, 1);
-        float mean_r = sum_ret / n;
-        float var_r = fmaxf(sum_ret2 / n - mean_r * mean_r, 0.0f);
-        float sharpe =
-            mean_r / fmaxf(sqrtf(var_r), BT_EPS) * BT_ANNUALIZE;
-        if (!(n_trades > 0.0f)) sharpe = 0.0f;
-        float win_rate = wins / fmaxf(n_trades, 1.0f);
-        float fitness = (n_trades > 0.0f)
-                            ? sharpe + win_rate - 2.0f * max_dd
-                            : -1.0f;
-        float* out =
-            metrics + ((long)p * nsym_stride + sym0 + sym) * BT_NMETRIC;
-        out[0] = equity; out[1] = n_trades; out[2] = wins;
-        out[3] = gross_p; out[4] = gross_l; out[5] = max_dd;
-        out[6] = sum_ret; out[7] = sum_ret2;
-        out[8] = sharpe; out[9] = fitness;
-    }
+    if (!is_prod && act)
+        bt_write_metrics(
+            metrics + ((long)p * nsym_stride + sym0 + sym) * BT_NMETRIC, T,
+            eqbuf[0][0][lane], eqbuf[0][1][lane], eqbuf[0][2][lane],
+            eqbuf[0][3][lane], eqbuf[0][4][lane], max_dd, sum_ret,
+            sum_ret2);
 }
 
 }  // namespace

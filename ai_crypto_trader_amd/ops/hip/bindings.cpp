@@ -11,6 +11,8 @@
 #include <stdexcept>
 #include <string>
 
+#include "bt_vote.hpp"
+
 namespace py = pybind11;
 
 extern "C" void launch_bt_flags(const float*, const float*,
@@ -97,6 +99,15 @@ static hipStream_t as_stream(uintptr_t s) {
 PYBIND11_MODULE(_hip_ops, m) {
     m.doc() = "MI355X (gfx950) kernels for ai_crypto_trader_amd";
     m.attr("GFX_ARCH") = "gfx950";
+    // the vote-family contract as compiled into the kernels;
+    // ops/backtest.py checks it against backtesting/strategy.py
+    m.attr("BT_NPARAM") = BT_NPARAM;
+    m.attr("BT_NMETRIC") = BT_NMETRIC;
+    m.attr("BT_MAXWIN") = BT_MAXWIN;
+    m.attr("BT_HALO") = BT_HALO;
+    m.attr("BT_WARMUP") = BT_WARMUP;
+    m.attr("BT_RESNAP") = BT_RESNAP;
+    m.attr("BT_NSTATE") = BT_NSTATE;
 
     m.def("backtest",
           [](uintptr_t candles, uintptr_t pop, uintptr_t metrics, int nsym,

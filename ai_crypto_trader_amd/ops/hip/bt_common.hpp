@@ -1,0 +1,98 @@
+// What every backtest kernel shares (backtest.hip, backtest_tp.hip,
+// backtest_grid.hip, backtest_dca.hip): the block geometry, the 10-slot
+// metrics vector with its mark-to-market and finalize formula
+// (engine_cpu.finalize_metrics), and the XCD-affine block map — so
+// everything downstream of the metrics tensor is family-agnostic and a
+// contract change lands in one place.
+#pragma once
+
+#include "common.hpp"
+
+#define BT_BLOCK 256
+#define BT_TILE 256
+#define BT_NMETRIC 10            // == engine_cpu.py NMETRIC
+#define BT_FEE 0.001f            // == strategy.py FEE
+#define BT_EPS 1e-9f
+// float32(sqrt(525600)) EXACTLY (0x44353ee6) — a shorter decimal literal
+// rounds to the neighbor 0x44353ee5 and biases every sharpe by 1 ulp
+#define BT_ANNUALIZE 0x1.6a7dccp+9f
+
+// The ten metrics from scalars (engine_cpu.finalize_metrics semantics).
+// A free function because bt_trades_kernel holds the inputs in two
+// different waves' registers, not in one BtAccum.
+__device__ inline void bt_write_metrics(
+    float* __restrict__ out, int T, float equity, float n_trades,
+    float wins, float gross_p, float gross_l, float max_dd, float sum_ret,
+    float sum_ret2)
+{
+#pragma clang fp contract(off)
+    float n = (float)max(T, 1);
+    float mean_r = sum_ret / n;
+    float var_r = fmaxf(sum_ret2 / n - mean_r * mean_r, 0.0f);
+    float sharpe = mean_r / fmaxf(sqrtf(var_r), BT_EPS) * BT_ANNUALIZE;
+    if (!(n_trades > 0.0f)) sharpe = 0.0f;
+    float win_rate = wins / fmaxf(n_trades, 1.0f);
+    float fitness = (n_trades > 0.0f)
+                        ? sharpe + win_rate - 2.0f * max_dd
+                        : -1.0f;
+    out[0] = equity; out[1] = n_trades; out[2] = wins;
+    out[3] = gross_p; out[4] = gross_l; out[5] = max_dd;
+    out[6] = sum_ret; out[7] = sum_ret2;
+    out[8] = sharpe; out[9] = fitness;
+}
+
+// equity / trade accounting of one lane
+struct BtAccum {
+    float equity, max_eq, max_dd;
+    float n_trades, wins, gross_p, gross_l;
+    float sum_ret, sum_ret2;
+
+    __device__ void init(float initial_equity)
+    {
+        equity = initial_equity; max_eq = initial_equity; max_dd = 0.f;
+        n_trades = wins = gross_p = gross_l = 0.f;
+        sum_ret = sum_ret2 = 0.f;
+    }
+
+    __device__ void trade(float pnl)
+    {
+        n_trades += 1.0f;
+        wins += (pnl > 0.0f) ? 1.0f : 0.0f;
+        gross_p += fmaxf(pnl, 0.0f);
+        gross_l += fmaxf(-pnl, 0.0f);
+    }
+
+    __device__ void mark(float new_eq)
+    {
+#pragma clang fp contract(off)
+        float r = new_eq / equity - 1.0f;
+        sum_ret += r;
+        sum_ret2 += r * r;
+        equity = new_eq;
+        max_eq = fmaxf(max_eq, equity);
+        max_dd = fmaxf(max_dd, (max_eq - equity) / max_eq);
+    }
+
+    __device__ void finalize(float* __restrict__ out, int T) const
+    {
+        bt_write_metrics(out, T, equity, n_trades, wins, gross_p, gross_l,
+                         max_dd, sum_ret, sum_ret2);
+    }
+};
+
+// block -> (symbol, param chunk): same-symbol blocks share an XCD when the
+// shape allows (the dispatcher places block b on XCD b%8), so one symbol's
+// candle stream stays in one XCD's L2.
+__device__ inline void bt_block_map(int bid, int nsym, int chunks_per_sym,
+                                    int& sym, int& chunk)
+{
+    int nblocks = nsym * chunks_per_sym;
+    if ((nsym & 7) == 0 && (nblocks & 7) == 0) {
+        int xcd = bid & 7, j = bid >> 3;
+        sym = xcd + 8 * (j / chunks_per_sym);
+        chunk = j % chunks_per_sym;
+    } else {
+        sym = bid / chunks_per_sym;
+        chunk = bid % chunks_per_sym;
+    }
+}

@@ -1,0 +1,223 @@
+// The vote-family contract of backtesting/strategy.py, once, for every
+// kernel that implements it (backtest.hip marches it sequentially,
+// backtest_tp.hip's bt_flags_kernel time-parallel): constants, parameter
+// decode, the per-candle indicator recurrences + six-vote count, the
+// Bollinger resnap, and the per-tile LDS staging / shared-series
+// precompute. All of it matches backtesting/engine_cpu.py bit for bit
+// (fp-contract off, same operation order, f64 Bollinger sums both sides).
+#pragma once
+
+#include "bt_common.hpp"
+
+#define BT_NPARAM 19           // == strategy.py NPARAM
+#define BT_MAXWIN 32           // == strategy.py MAX_WIN
+#define BT_HALO 64             // == strategy.py SHARED_HALO (covers sma50)
+#define BT_SPAN (BT_TILE + BT_HALO)
+#define BT_WARMUP 128          // == strategy.py WARMUP
+#define BT_RESNAP 16384        // == strategy.py RESNAP (BB sum resnap)
+// floats per (param, symbol) that bt_trades_kernel carries between its
+// chunked launches; ops/backtest.py sizes the carry buffer from it
+#define BT_NSTATE 18
+
+// decoded indicator/vote parameters + recurrence state of one strategy
+struct VoteState {
+    float inv_rsi_p, rsi_os, rsi_ob;
+    float a_f, a_s, a_sig;
+    int bb_w;
+    float bb_k, bb_bth, bb_sth;
+    int entry_v, exit_v;
+    float stoch_os, stoch_ob, will_os, will_ob;
+
+    float ema_f, ema_s, sig;
+    float avg_gain, avg_loss;
+    double bb_sum, bb_sum2, inv_w;    // f64 sums: f32 drifts + cancels
+
+    __device__ void load(const float* __restrict__ pr)
+    {
+        inv_rsi_p = 1.0f / fmaxf(floorf(pr[0]), 1.0f);
+        rsi_os = pr[1]; rsi_ob = pr[2];
+        a_f = 2.0f / (pr[3] + 1.0f);
+        a_s = 2.0f / (pr[4] + 1.0f);
+        a_sig = 2.0f / (pr[5] + 1.0f);
+        bb_w = min(max((int)pr[6], 2), BT_MAXWIN);
+        bb_k = pr[7]; bb_bth = pr[8]; bb_sth = pr[9];
+        entry_v = (int)pr[10]; exit_v = (int)pr[11];
+        stoch_os = pr[17]; stoch_ob = pr[18];
+        will_os = stoch_os - 100.0f;
+        will_ob = stoch_ob - 100.0f;
+        ema_f = ema_s = sig = 0.f;
+        avg_gain = avg_loss = 0.f;
+        bb_sum = bb_sum2 = 0.0;
+        inv_w = 1.0 / (double)bb_w;
+    }
+
+    // Drift-free Bollinger resnap (strategy.py RESNAP): recompute the
+    // window sums directly, oldest->newest, from the close history.
+    // `hist` points at close[t] (the resnap candle itself, j = 0 term).
+    // (noinline was tried here: 86 VGPR/no spills but the call
+    // inside the tile loop cost 25% — inlined + launch-bounds wins)
+    __device__ void resnap(const float* __restrict__ hist)
+    {
+#pragma clang fp contract(off)
+        double s = 0.0, s2 = 0.0;
+        const int w = bb_w;
+        for (int j = BT_MAXWIN - 1; j >= 0; --j) {
+            if (j < w) {
+                double c = (double)hist[-j];
+                s += c;
+                s2 += c * c;
+            }
+        }
+        bb_sum = s;
+        bb_sum2 = s2;
+    }
+
+    // warm-tail march: the same f32 recurrence ops as step(), minus
+    // Bollinger (resnapped at body start) and votes
+    __device__ void warm_step(float close, float change)
+    {
+#pragma clang fp contract(off)
+        ema_f += a_f * (close - ema_f);
+        ema_s += a_s * (close - ema_s);
+        float macd = ema_f - ema_s;
+        sig += a_sig * (macd - sig);
+        float gain = fmaxf(change, 0.0f);
+        float loss = fmaxf(-change, 0.0f);
+        avg_gain += (gain - avg_gain) * inv_rsi_p;
+        avg_loss += (loss - avg_loss) * inv_rsi_p;
+    }
+
+    // One candle: indicators + the 6-indicator TradingSignal vote count;
+    // returns net = buys - sells (0 before WARMUP). `oldc` is
+    // close[t - bb_w]; csq_new / csq_old are (double)close^2 and
+    // (double)oldc^2, passed in so a caller may share them through LDS.
+    // SKIP_BB is a compile-time flag (a resnap() just replaced the sums
+    // for this candle) so the steady-state loop carries no per-candle
+    // branch — the resnap candle is peeled at the call site.
+    template <bool SKIP_BB>
+    __device__ int step(int t, float close, float change, float oldc,
+                        double csq_new, double csq_old, float4 sv)
+    {
+#pragma clang fp contract(off)           // match the numpy f32 reference
+        if (t == 0) { ema_f = close; ema_s = close; }
+        else {
+            ema_f += a_f * (close - ema_f);
+            ema_s += a_s * (close - ema_s);
+        }
+        float macd = ema_f - ema_s;
+        sig += a_sig * (macd - sig);
+        float macd_hist = macd - sig;
+
+        float gain = fmaxf(change, 0.0f);
+        float loss = fmaxf(-change, 0.0f);
+        avg_gain += (gain - avg_gain) * inv_rsi_p;
+        avg_loss += (loss - avg_loss) * inv_rsi_p;
+        // division-free RSI votes (engine_cpu.py): rsi<thr <=>
+        // 100*ag < thr*(ag+al')
+        float rsi_num = 100.0f * avg_gain;
+        float rsi_den = avg_gain + fmaxf(avg_loss, BT_EPS);
+
+        // Bollinger: close[t - W] comes from the shared halo tile
+        // (== the zero-initialized per-lane ring of engine_cpu.py)
+        if (!SKIP_BB) {
+            double old = (double)oldc;
+            double c64 = (double)close;
+            bb_sum += c64 - old;
+            bb_sum2 += csq_new - csq_old;
+        }
+        double inv_cnt = inv_w;
+        // the early-window divisor only exists in the very first tile
+        // (t < MAX_WIN <= 32 < BT_TILE): uniformly skipped t>=32
+        if (t < BT_MAXWIN && t + 1 < bb_w)
+            inv_cnt = 1.0 / (t + 1.0);
+        double mean64 = bb_sum * inv_cnt;
+        double var64 = fmax(bb_sum2 * inv_cnt - mean64 * mean64, 0.0);
+        float mean = (float)mean64;
+        float std_ = sqrtf((float)var64);
+        float band = bb_k * std_;
+        // division-free BB votes (engine_cpu.py): pos<thr <=> num<thr*den
+        float bb_num = close - (mean - band);
+        float bb_den = fmaxf(2.0f * band, BT_EPS);
+
+        int net = 0;
+        if (t >= BT_WARMUP) {
+            int buy = (rsi_num < rsi_os * rsi_den) +
+                      (macd_hist > 0.0f) +
+                      (bb_num < bb_bth * bb_den) +
+                      (sv.x < stoch_os * sv.z) +
+                      (sv.y < will_os * sv.z) +
+                      (sv.w > 0.0f);
+            int sell = (rsi_num > rsi_ob * rsi_den) +
+                       (macd_hist < 0.0f) +
+                       (bb_num > bb_sth * bb_den) +
+                       (sv.x > stoch_ob * sv.z) +
+                       (sv.y > will_ob * sv.z) +
+                       (sv.w < 0.0f);
+            net = buy - sell;
+        }
+        return net;
+    }
+};
+
+// Stage candles [t0 - HALO, t0 + TILE) of one symbol into LDS, zero-filled
+// outside [0, T): closes into chist, (high, low) into hl and, when csq is
+// given, (double)close^2 into csq. Barriers on both sides: the previous
+// tile's readers are done before, the tile is visible after.
+__device__ inline void bt_stage_tile(
+    const float4* __restrict__ sym_candles, int t0, int T,
+    float* __restrict__ chist, float (*__restrict__ hl)[2],
+    double* __restrict__ csq)
+{
+#pragma clang fp contract(off)
+    __syncthreads();
+    for (int i = threadIdx.x; i < BT_SPAN; i += BT_BLOCK) {
+        const int t = t0 - BT_HALO + i;
+        float4 c = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        if (t >= 0 && t < T) c = sym_candles[t];
+        chist[i] = c.x;
+        if (csq) csq[i] = (double)c.x * (double)c.x;
+        hl[i][0] = c.y;
+        hl[i][1] = c.z;
+    }
+    __syncthreads();
+}
+
+// Param-independent shared vote inputs of tile candles [t0, t0 + tend),
+// one thread per candle (strategy.py step-1 spec: every lane of a symbol
+// shares them), packed {st_num, wl_num, srange, trend}: st_num =
+// 100*(close-lmin14), wl_num = -100*(hmax14-close), srange =
+// max(hmax-lmin, eps), trend = +-1/0 from close vs sma20/50 — so the
+// lane loop needs one b128 broadcast read per candle. Finite windows over
+// the staged halo: exact wherever the tile starts. The caller's barrier
+// publishes sh_vote.
+__device__ inline void bt_shared_votes(
+    int t0, int tend, const float* __restrict__ chist,
+    const float (*__restrict__ hl)[2], float4* __restrict__ sh_vote)
+{
+#pragma clang fp contract(off)
+    const int tid = threadIdx.x;
+    if (tid >= tend) return;
+    const int t = t0 + tid;
+    const int base = tid + BT_HALO;
+    const float cl = chist[base];
+    const int L14 = min(t + 1, 14);
+    float hmax = -1e30f, lmin = 1e30f;
+    for (int j = 0; j < L14; ++j) {
+        hmax = fmaxf(hmax, hl[base - j][0]);
+        lmin = fminf(lmin, hl[base - j][1]);
+    }
+    const int L20 = min(t + 1, 20);
+    double s20 = 0.0;
+    for (int j = 0; j < L20; ++j) s20 += (double)chist[base - j];
+    const float sma20 = (float)(s20 / (double)L20);
+    const int L50 = min(t + 1, 50);
+    double s50 = 0.0;
+    for (int j = 0; j < L50; ++j) s50 += (double)chist[base - j];
+    const float sma50 = (float)(s50 / (double)L50);
+    const float trend = (cl > sma20 && sma20 > sma50) ? 1.0f
+                        : ((cl < sma20 && sma20 < sma50) ? -1.0f
+                                                         : 0.0f);
+    sh_vote[tid] = make_float4(
+        100.0f * (cl - lmin), -100.0f * (hmax - cl),
+        fmaxf(hmax - lmin, BT_EPS), trend);
+}
