@@ -70,6 +70,11 @@ class NNConfig(BaseModel):
     # NN feature attribution (SHAP stand-in): grad_input |
     # integrated_gradients (neural_network_service.py:957-1003)
     attribution: str = "integrated_gradients"
+    # train/serve all ready symbols as one stacked model (train_many /
+    # predict_many, models/lstm_multi.py) when at least two are ready;
+    # on by default: 7.7x the serial loop's training throughput at the
+    # service shape (9 models x batch 32, docs/KERNELS.md)
+    stacked: bool = True
 
 
 class EvolutionConfig(BaseModel):

@@ -58,6 +58,13 @@ extern "C" void launch_lstm_seq_fwd(const void*, const void*, const float*,
 extern "C" void launch_lstm_seq_bwd(const float*, const void*, const float*,
                                     const void*, void*, int, int, int,
                                     hipStream_t);
+extern "C" void launch_lstm_seq_fwd_multi(const void*, const void*,
+                                          const float*, void*, void*, float*,
+                                          int, int, int, int, int,
+                                          hipStream_t);
+extern "C" void launch_lstm_seq_bwd_multi(const float*, const void*,
+                                          const float*, const void*, void*,
+                                          int, int, int, int, hipStream_t);
 extern "C" void launch_mfma_gemm_test(const void*, const void*, float*, int,
                                       int, int, hipStream_t);
 extern "C" void launch_mfma_gemm_test_bf16(const void*, const void*, float*,
@@ -328,6 +335,36 @@ PYBIND11_MODULE(_hip_ops, m) {
                                   reinterpret_cast<void*>(dgates_out), B, T,
                                   H, as_stream(stream));
               check(hipGetLastError(), "lstm_seq_bwd launch");
+          });
+
+    // M independent models per launch; all arrays model-major
+    m.def("lstm_seq_fwd_multi",
+          [](uintptr_t xproj, uintptr_t Wt, uintptr_t bias, uintptr_t h_out,
+             uintptr_t gates_out, uintptr_t c_out, int M, int B, int T,
+             int H, int save_mode, uintptr_t stream) {
+              launch_lstm_seq_fwd_multi(
+                  reinterpret_cast<const void*>(xproj),
+                  reinterpret_cast<const void*>(Wt),
+                  reinterpret_cast<const float*>(bias),
+                  reinterpret_cast<void*>(h_out),
+                  reinterpret_cast<void*>(gates_out),
+                  reinterpret_cast<float*>(c_out), M, B, T, H, save_mode,
+                  as_stream(stream));
+              check(hipGetLastError(), "lstm_seq_fwd_multi launch");
+          });
+
+    m.def("lstm_seq_bwd_multi",
+          [](uintptr_t dh_up, uintptr_t gates, uintptr_t c_sav, uintptr_t W,
+             uintptr_t dgates_out, int M, int B, int T, int H,
+             uintptr_t stream) {
+              launch_lstm_seq_bwd_multi(
+                  reinterpret_cast<const float*>(dh_up),
+                  reinterpret_cast<const void*>(gates),
+                  reinterpret_cast<const float*>(c_sav),
+                  reinterpret_cast<const void*>(W),
+                  reinterpret_cast<void*>(dgates_out), M, B, T, H,
+                  as_stream(stream));
+              check(hipGetLastError(), "lstm_seq_bwd_multi launch");
           });
 
     m.def("env_reset",

@@ -27,6 +27,9 @@
 // batched reductions dW_hh = sum_t h_{t-1}^T dgates_t, dW_ih, db are
 // single hipBLASLt GEMMs on the torch side (models/lstm.py).
 
+#include <stdexcept>
+#include <string>
+
 #include "common.hpp"
 
 typedef __bf16 bf16;
@@ -34,9 +37,9 @@ typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 #define LSTM_MT 4           // M-tiles per wave (batch tile = 16*MT rows)
-#define LSTM_BM (16 * LSTM_MT)   // 32-row batch tiles: 2x the blocks of a
-                                 // 64-row tile -> 2 blocks/CU at B=16384
-                                 // (B/64 blocks was exactly 1/CU: latency-bound)
+#define LSTM_BM (16 * LSTM_MT)   // 64-row batch tiles: B/64 blocks per model
+                                 // (1 block/CU at B=16384; the multi-model
+                                 // launchers add a model axis, grid.y)
 
 namespace {
 
@@ -51,14 +54,17 @@ DEV_INLINE float tanhf_(float x) {
     return 2.0f * __builtin_amdgcn_rcpf(1.0f + __expf(-2.0f * x)) - 1.0f;
 }
 
-template <int H>
+// MULTI adds the model axis: blockIdx.y = model over model-major slabs,
+// each exactly the single-model layout. The single-model launchers keep
+// the MULTI = false instantiations, whose code has no model arithmetic.
+template <int H, bool MULTI>
 __global__ void __launch_bounds__((H / 16) * 64) lstm_seq_fwd_kernel(
-    const bf16* __restrict__ xproj,    // (T, B, 4H)  x@W_ih + b_ih (bf16)
-    const bf16* __restrict__ Wt,       // (4H, H)     W_hh transposed, n-major
-    const float* __restrict__ bias,    // (4H,)       b_hh
-    bf16* __restrict__ h_out,          // (T, B, H)
-    bf16* __restrict__ gates_out,      // (T, B, 4H)  post-activation i,f,g,o
-    float* __restrict__ c_out,         // (T, B, H)
+    const bf16* __restrict__ xproj,    // (M, T, B, 4H) x@W_ih + b_ih (bf16)
+    const bf16* __restrict__ Wt,       // (M, 4H, H)  W_hh transposed, n-major
+    const float* __restrict__ bias,    // (M, 4H)     b_hh
+    bf16* __restrict__ h_out,          // (M, T, B, H)
+    bf16* __restrict__ gates_out,      // (M, T, B, 4H) post-activation i,f,g,o
+    float* __restrict__ c_out,         // (M, T, B, H)
     int B, int T, int save_mode)       // 0: inference (h only), 1: training
 {
     constexpr int NW = H / 16;          // waves per block
@@ -75,6 +81,20 @@ __global__ void __launch_bounds__((H / 16) * 64) lstm_seq_fwd_kernel(
     const int w = tid >> 6;             // wave id = hidden sub-column
     const int fr = lane & 15;           // fragment col
     const int fq = lane >> 4;           // fragment row group / k group
+    if constexpr (MULTI) {
+        // per-model bases, 64-bit and wave-uniform: the per-lane index
+        // math below is the single-model one
+        const long model = blockIdx.y;
+        const long model_tb = model * T * B;   // row offset of this slab
+        xproj += model_tb * FOURH;
+        h_out += model_tb * H;
+        if (save_mode) {                       // null in inference mode
+            gates_out += model_tb * FOURH;
+            c_out += model_tb * H;
+        }
+        Wt += model * (FOURH * H);
+        bias += model * FOURH;
+    }
 
     // stage W_hh^T (4H x H) into LDS, padded rows
     for (int i = tid; i < FOURH * H; i += NW * 64)
@@ -164,13 +184,13 @@ __global__ void __launch_bounds__((H / 16) * 64) lstm_seq_fwd_kernel(
     }
 }
 
-template <int H>
+template <int H, bool MULTI>
 __global__ void __launch_bounds__((H / 16) * 64) lstm_seq_bwd_kernel(
-    const float* __restrict__ dh_up,   // (T, B, H) upstream grad
-    const bf16* __restrict__ gates,    // (T, B, 4H) saved i,f,g,o
-    const float* __restrict__ c_sav,   // (T, B, H)
-    const bf16* __restrict__ W,        // (H, 4H)  W_hh row-major
-    bf16* __restrict__ dgates_out,     // (T, B, 4H)
+    const float* __restrict__ dh_up,   // (M, T, B, H) upstream grad
+    const bf16* __restrict__ gates,    // (M, T, B, 4H) saved i,f,g,o
+    const float* __restrict__ c_sav,   // (M, T, B, H)
+    const bf16* __restrict__ W,        // (M, H, 4H)  W_hh row-major
+    bf16* __restrict__ dgates_out,     // (M, T, B, 4H)
     int B, int T)
 {
     constexpr int NW = H / 16;
@@ -187,6 +207,15 @@ __global__ void __launch_bounds__((H / 16) * 64) lstm_seq_bwd_kernel(
     const int w = tid >> 6;
     const int fr = lane & 15;
     const int fq = lane >> 4;
+    if constexpr (MULTI) {                  // as in the forward kernel
+        const long model = blockIdx.y;
+        const long model_tb = model * T * B;
+        dh_up += model_tb * H;
+        gates += model_tb * FOURH;
+        c_sav += model_tb * H;
+        dgates_out += model_tb * FOURH;
+        W += model * (H * FOURH);
+    }
 
     for (int i = tid; i < H * FOURH; i += NW * 64)
         lds_w[(i / FOURH) * GP + (i % FOURH)] = W[i];
@@ -294,47 +323,96 @@ __global__ void mfma_gemm_test_bf16_kernel(const bf16* __restrict__ A,
 
 }  // namespace
 
+// Shared launchers: grid = (B/64 batch tiles, M models). The single-model
+// entry points launch the MULTI = false instantiations with M = 1.
+template <bool MULTI>
+static void lstm_fwd_launch(const char* who, const void* xproj,
+                            const void* Wt, const float* bias, void* h_out,
+                            void* gates_out, float* c_out, int M, int B,
+                            int T, int H, int save_mode,
+                            hipStream_t stream) {
+    if (B <= 0 || B % LSTM_BM != 0)
+        throw std::runtime_error(std::string(who) +
+                                 ": B must be a multiple of 64");
+    if (M < 1 || M > 65535)
+        throw std::runtime_error(std::string(who) +
+                                 ": M must be in [1, 65535]");
+    dim3 grid(B / LSTM_BM, M);
+    if (H == 64) {
+        hipLaunchKernelGGL((lstm_seq_fwd_kernel<64, MULTI>), grid,
+                           dim3(256), 0, stream, (const bf16*)xproj,
+                           (const bf16*)Wt, bias, (bf16*)h_out,
+                           (bf16*)gates_out, c_out, B, T, save_mode);
+    } else if (H == 32) {
+        hipLaunchKernelGGL((lstm_seq_fwd_kernel<32, MULTI>), grid,
+                           dim3(128), 0, stream, (const bf16*)xproj,
+                           (const bf16*)Wt, bias, (bf16*)h_out,
+                           (bf16*)gates_out, c_out, B, T, save_mode);
+    } else {
+        throw std::runtime_error(std::string(who) + ": H must be 32 or 64");
+    }
+}
+
+template <bool MULTI>
+static void lstm_bwd_launch(const char* who, const float* dh_up,
+                            const void* gates, const float* c_sav,
+                            const void* W, void* dgates_out, int M, int B,
+                            int T, int H, hipStream_t stream) {
+    if (B <= 0 || B % LSTM_BM != 0)
+        throw std::runtime_error(std::string(who) +
+                                 ": B must be a multiple of 64");
+    if (M < 1 || M > 65535)
+        throw std::runtime_error(std::string(who) +
+                                 ": M must be in [1, 65535]");
+    dim3 grid(B / LSTM_BM, M);
+    if (H == 64) {
+        hipLaunchKernelGGL((lstm_seq_bwd_kernel<64, MULTI>), grid,
+                           dim3(256), 0, stream, dh_up, (const bf16*)gates,
+                           c_sav, (const bf16*)W, (bf16*)dgates_out, B, T);
+    } else if (H == 32) {
+        hipLaunchKernelGGL((lstm_seq_bwd_kernel<32, MULTI>), grid,
+                           dim3(128), 0, stream, dh_up, (const bf16*)gates,
+                           c_sav, (const bf16*)W, (bf16*)dgates_out, B, T);
+    } else {
+        throw std::runtime_error(std::string(who) + ": H must be 32 or 64");
+    }
+}
+
 extern "C" void launch_lstm_seq_fwd(const void* xproj, const void* Wt,
                                     const float* bias, void* h_out,
                                     void* gates_out, float* c_out, int B,
                                     int T, int H, int save_mode,
                                     hipStream_t stream) {
-    if (B % LSTM_BM != 0)
-        throw std::runtime_error("lstm_fwd: B must be a multiple of 64");
-    dim3 grid(B / LSTM_BM);
-    if (H == 64) {
-        hipLaunchKernelGGL(lstm_seq_fwd_kernel<64>, grid, dim3(256), 0,
-                           stream, (const bf16*)xproj, (const bf16*)Wt, bias,
-                           (bf16*)h_out, (bf16*)gates_out, c_out, B, T,
-                           save_mode);
-    } else if (H == 32) {
-        hipLaunchKernelGGL(lstm_seq_fwd_kernel<32>, grid, dim3(128), 0,
-                           stream, (const bf16*)xproj, (const bf16*)Wt, bias,
-                           (bf16*)h_out, (bf16*)gates_out, c_out, B, T,
-                           save_mode);
-    } else {
-        throw std::runtime_error("lstm_fwd: H must be 32 or 64");
-    }
+    lstm_fwd_launch<false>("lstm_fwd", xproj, Wt, bias, h_out, gates_out,
+                           c_out, 1, B, T, H, save_mode, stream);
 }
 
 extern "C" void launch_lstm_seq_bwd(const float* dh_up, const void* gates,
                                     const float* c_sav, const void* W,
                                     void* dgates_out, int B, int T, int H,
                                     hipStream_t stream) {
-    if (B % LSTM_BM != 0)
-        throw std::runtime_error("lstm_bwd: B must be a multiple of 64");
-    dim3 grid(B / LSTM_BM);
-    if (H == 64) {
-        hipLaunchKernelGGL(lstm_seq_bwd_kernel<64>, grid, dim3(256), 0,
-                           stream, dh_up, (const bf16*)gates, c_sav,
-                           (const bf16*)W, (bf16*)dgates_out, B, T);
-    } else if (H == 32) {
-        hipLaunchKernelGGL(lstm_seq_bwd_kernel<32>, grid, dim3(128), 0,
-                           stream, dh_up, (const bf16*)gates, c_sav,
-                           (const bf16*)W, (bf16*)dgates_out, B, T);
-    } else {
-        throw std::runtime_error("lstm_bwd: H must be 32 or 64");
-    }
+    lstm_bwd_launch<false>("lstm_bwd", dh_up, gates, c_sav, W, dgates_out,
+                           1, B, T, H, stream);
+}
+
+// M independent models in one launch; every array is model-major.
+extern "C" void launch_lstm_seq_fwd_multi(const void* xproj, const void* Wt,
+                                          const float* bias, void* h_out,
+                                          void* gates_out, float* c_out,
+                                          int M, int B, int T, int H,
+                                          int save_mode,
+                                          hipStream_t stream) {
+    lstm_fwd_launch<true>("lstm_fwd_multi", xproj, Wt, bias, h_out,
+                          gates_out, c_out, M, B, T, H, save_mode, stream);
+}
+
+extern "C" void launch_lstm_seq_bwd_multi(const float* dh_up,
+                                          const void* gates,
+                                          const float* c_sav, const void* W,
+                                          void* dgates_out, int M, int B,
+                                          int T, int H, hipStream_t stream) {
+    lstm_bwd_launch<true>("lstm_bwd_multi", dh_up, gates, c_sav, W,
+                          dgates_out, M, B, T, H, stream);
 }
 
 extern "C" void launch_mfma_gemm_test_bf16(const void* A, const void* B,

@@ -84,6 +84,10 @@ class NeuralNetworkService(Service):
         self.candles: dict[str, list] = {}
         self.trained = 0
         self.predictions = 0
+        # shapes of the last train_many() run (symbols, candles, windows)
+        self.last_train_many: dict | None = None
+        # predict_many()'s stacked module: (models, param versions, module)
+        self._stacked_cache: tuple | None = None
 
     def run_tasks(self):
         return [self._consume_market(), self._train_loop(),
@@ -151,6 +155,121 @@ class NeuralNetworkService(Service):
         self.val_loss[sym] = best_val
         self.trained += 1
         return best_val
+
+    def train_many(self, data: dict[str, np.ndarray],
+                   epochs: int | None = None,
+                   batch: int | None = None) -> dict[str, float]:
+        """train() for several symbols as ONE stacked model
+        (models/lstm_multi.py): per step one fused multi-model recurrence
+        launch per layer and one Adam over the stacked parameters, instead
+        of a launch sequence per symbol.
+
+        Features, per-symbol MinMaxScaler, windows, the 10 % validation
+        tail and per-model early stopping (patience 5, 1e-6 improvement)
+        are train()'s. Differences that stacking needs:
+          * histories are tail-aligned to the shortest trainable one — the
+            most recent candles are kept, older ones of longer histories
+            are not used;
+          * every epoch draws one torch.randperm shared by all models;
+          * the loss is the SUM over models of each model's mean squared
+            error, so each model's gradient is what it would get alone;
+          * a model that stopped early is frozen: its slice is restored
+            after every later step (Adam momentum would otherwise still
+            move it).
+        A symbol with fewer than 64 windows is left out and returns nan.
+        Existing models are the starting weights; results are written back
+        as ordinary LSTMPricePredictors."""
+        from ..models.lstm_multi import StackedLSTMPricePredictor
+
+        cfg = self.config.neural_network
+        out = {sym: float("nan") for sym in data}
+        syms = [s for s, c in data.items()
+                if len(c) - cfg.seq_len >= 64]
+        if not syms:
+            return out
+        n_candles = min(len(data[s]) for s in syms)
+        scalers, Xs, ys = [], [], []
+        for sym in syms:
+            candles = np.asarray(data[sym], np.float32)[-n_candles:]
+            feats = build_features(candles)
+            targets = np.zeros(len(feats), np.float32)
+            close = candles[:, 0]
+            targets[:-1] = (close[1:] / close[:-1] - 1.0) * 100.0
+            scaler = MinMaxScaler().fit(feats)
+            X, y = make_windows(scaler.transform(feats), targets,
+                                cfg.seq_len)
+            scalers.append(scaler)
+            Xs.append(X)
+            ys.append(y)
+        X = torch.from_numpy(np.stack(Xs).astype(np.float32))  # (M,N,T,F)
+        y = torch.from_numpy(np.stack(ys).astype(np.float32))  # (M,N)
+        n_win = X.shape[1]
+        n_val = max(n_win // 10, 1)
+        Xt = X[:, :-n_val].to(self.device)
+        yt = y[:, :-n_val].to(self.device)
+        Xv = X[:, -n_val:].to(self.device)
+        yv = y[:, -n_val:].to(self.device)
+
+        singles = []
+        for sym in syms:
+            model = self.models.get(sym)
+            if model is None:
+                model = LSTMPricePredictor(
+                    n_features=N_FEAT, seq_len=cfg.seq_len,
+                    hidden=tuple(cfg.hidden)).to(self.device)
+            singles.append(model)
+        stacked = StackedLSTMPricePredictor.from_models(singles)
+        opt = torch.optim.Adam(stacked.parameters(), lr=cfg.lr)
+        bs = batch or cfg.batch_size
+        M = len(syms)
+        best_val = [float("inf")] * M
+        bad = [0] * M
+        frozen: dict[int, list[torch.Tensor]] = {}
+        patience = 5
+        n_train = Xt.shape[1]
+        for ep in range(epochs or min(cfg.epochs, 10)):
+            perm = torch.randperm(n_train, device=self.device)
+            for i in range(0, n_train, bs):
+                j = perm[i:i + bs]
+                self._stacked_step(stacked, opt, Xt[:, j], yt[:, j], frozen)
+            with torch.no_grad():
+                vls = ((stacked(Xv) - yv) ** 2).mean(dim=1).tolist()
+            for m in range(M):
+                if m in frozen:
+                    continue
+                if vls[m] < best_val[m] - 1e-6:
+                    best_val[m], bad[m] = vls[m], 0
+                else:
+                    bad[m] += 1
+                    if bad[m] >= patience:     # per-model EarlyStopping
+                        frozen[m] = stacked.snapshot_model(m)
+            if len(frozen) == M:
+                break
+        for m, sym in enumerate(syms):
+            self.models[sym] = stacked.export_model(m)
+            self.scalers[sym] = scalers[m]
+            self.val_loss[sym] = best_val[m]
+            out[sym] = best_val[m]
+        self.trained += M
+        self.last_train_many = {"symbols": list(syms), "candles": n_candles,
+                                "windows": n_win, "train_windows": n_train,
+                                "val_windows": n_val}
+        return out
+
+    @staticmethod
+    def _stacked_step(stacked, opt, xb: torch.Tensor, yb: torch.Tensor,
+                      frozen: dict[int, list[torch.Tensor]]) -> torch.Tensor:
+        """One Adam step on the summed per-model-mean loss. Models in
+        `frozen` (index -> snapshot_model() tensors) are put back
+        afterwards, so they stay bit-identical while the rest train.
+        Returns the per-model losses (M,)."""
+        opt.zero_grad()
+        per_model = ((stacked(xb) - yb) ** 2).mean(dim=1)
+        per_model.sum().backward()
+        opt.step()
+        for m, snap in frozen.items():
+            stacked.restore_model(m, snap)
+        return per_model.detach()
 
     def snapshot_for_regime(self, sym: str, regime: str):
         """Regime-specific model snapshot (reference
@@ -232,6 +351,64 @@ class NeuralNetworkService(Service):
     FEATURE_NAMES = ["close", "high", "low", "volume", "rsi",
                      "macd_hist", "bb_position", "return_1", "atr"]
 
+    def _stacked_for(self, models: list[LSTMPricePredictor]):
+        """Stacked module for exactly these model objects, rebuilt when
+        any of them is a different object or has been written to since
+        (tensor version counters move on every optimizer step or load)."""
+        from ..models.lstm_multi import StackedLSTMPricePredictor
+
+        versions = [p._version for m in models for p in m.parameters()]
+        c = self._stacked_cache
+        if (c is not None and len(c[0]) == len(models)
+                and all(a is b for a, b in zip(c[0], models))
+                and c[1] == versions):
+            return c[2]
+        stacked = StackedLSTMPricePredictor.from_models(models)
+        stacked.requires_grad_(False)
+        self._stacked_cache = (list(models), versions, stacked)
+        return stacked
+
+    def predict_many(self, data: dict[str, np.ndarray],
+                     regime: str | None = None) -> dict[str, dict | None]:
+        """predict() for several symbols with ONE stacked no-grad forward.
+        Same tail clipping, scaler, confidence formula and payload; a
+        symbol without a model/scaler or with too little history maps to
+        None."""
+        cfg = self.config.neural_network
+        out: dict[str, dict | None] = {sym: None for sym in data}
+        syms, models, xs, prices = [], [], [], []
+        for sym, candles in data.items():
+            model, scaler = self.model_for(sym, regime)
+            if model is None or scaler is None:
+                continue
+            candles = np.asarray(candles, np.float32)[-(cfg.seq_len + 512):]
+            feats = build_features(candles)[-cfg.seq_len:]
+            if len(feats) < cfg.seq_len:
+                continue
+            syms.append(sym)
+            models.append(model)
+            xs.append(scaler.transform(feats)[None].astype(np.float32))
+            prices.append(float(candles[-1, 0]))
+        if not syms:
+            return out
+        x = torch.from_numpy(np.stack(xs)).to(self.device)   # (M, 1, T, F)
+        stacked = self._stacked_for(models)
+        with torch.no_grad():
+            changes = stacked(x)[:, 0].tolist()
+        for sym, price, change_pct in zip(syms, prices, changes):
+            vl = self.val_loss.get(sym, 1.0)
+            conf = float(np.clip(1.0 / (1.0 + 10.0 * vl), 0.05, 0.99))
+            out[sym] = NNPrediction(
+                symbol=sym, interval="1m",
+                predicted_price=price * (1 + change_pct / 100.0),
+                current_price=price,
+                predicted_change_pct=change_pct,
+                confidence=conf,
+                training_metrics={"val_loss": round(vl, 6)},
+                features_used=list(self.FEATURE_NAMES),
+            ).to_dict()
+        return out
+
     def feature_importance(self, sym: str, candles: np.ndarray) -> dict | None:
         """Per-input-feature attribution on the fused-LSTM predictor —
         the offline counterpart of the reference's SHAP DeepExplainer
@@ -306,7 +483,20 @@ class NeuralNetworkService(Service):
         }
 
     async def _train_loop(self):
+        stacked = getattr(self.config.neural_network, "stacked", False)
         while self.running:
+            ready = {sym: np.asarray(h, np.float32)
+                     for sym, h in list(self.candles.items())
+                     if len(h) >= 256 and sym not in self.models}
+            if stacked and len(ready) >= 2:
+                try:
+                    vls = self.train_many(ready, epochs=2)
+                    self.log.info("trained %d symbols stacked: %s",
+                                  len(vls), vls)
+                except Exception as e:
+                    self.log.warning("stacked train failed: %s", e)
+                await self.sleep(10.0)
+                continue
             for sym, h in list(self.candles.items()):
                 if len(h) >= 256 and sym not in self.models:
                     try:
@@ -318,7 +508,20 @@ class NeuralNetworkService(Service):
             await self.sleep(10.0)
 
     async def _predict_loop(self):
+        stacked = getattr(self.config.neural_network, "stacked", False)
         while self.running:
+            ready = {sym: np.asarray(h, np.float32)
+                     for sym, h in list(self.candles.items())
+                     if sym in self.models}
+            if stacked and len(ready) >= 2:
+                for p in self.predict_many(ready).values():
+                    if p:
+                        await self.bus.set(
+                            Keys.nn_prediction(p["symbol"], "1m"), p)
+                        await self.bus.publish(Channels.NN_PREDICTIONS, p)
+                        self.predictions += 1
+                await self.sleep(5.0)
+                continue
             for sym, h in list(self.candles.items()):
                 if sym in self.models:
                     p = self.predict(sym, np.asarray(h, np.float32))

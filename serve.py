@@ -6,6 +6,10 @@ and serves:
   POST /predict        {symbol, candles: [[close,high,low,vol],...]}
                        -> next-change prediction (fused-kernel inference
                           path: no backward saves, models/lstm.py)
+  POST /predict_many   {candles: {symbol: [[close,high,low,vol],...]}}
+                       -> {symbol: prediction}; with
+                          neural_network.stacked, cold symbols are trained
+                          and all are served as one stacked model
   POST /analyze        market-update dict -> LocalAnalyst decision
   POST /scan           {symbol: candles} -> ranked opportunities (one
                           batched GPU indicator launch)
@@ -64,6 +68,27 @@ def build_server(model_dir: str, device: str):
             with torch.no_grad():
                 out = nn.predict(sym, candles)
         return out or {"error": "insufficient history"}
+
+    @app.post("/predict_many")
+    async def predict_many(body: dict):
+        data = {s: np.asarray(c, np.float32)
+                for s, c in body["candles"].items()}
+        cold = {s: c for s, c in data.items() if s not in nn.models}
+        stacked = cfg.neural_network.stacked
+        if stacked and len(cold) >= 2:
+            # cold start of several symbols: one stacked training run
+            nn.train_many(cold, epochs=2)
+        else:
+            for s, c in cold.items():
+                nn.train(s, c, epochs=2)
+        with GpuTimer(metrics, "serve_predict_many"):
+            if stacked and len(data) >= 2:
+                out = nn.predict_many(data)
+            else:
+                with torch.no_grad():
+                    out = {s: nn.predict(s, c) for s, c in data.items()}
+        return {s: p or {"error": "insufficient history"}
+                for s, p in out.items()}
 
     @app.post("/analyze")
     async def analyze(body: dict):

@@ -8,7 +8,11 @@ bench.py headline:
   #4  PPO agent — 256 synthetic-market envs stepped by the HIP env
       kernel, GAE on the HIP reverse-scan kernel, full train_step.
 
+  multi  M per-symbol LSTM predictors, stacked (one model-axis launch,
+      models/lstm_multi.py) vs the serial per-symbol loop.
+
   python tools/bench_train.py [--workload lstm|ppo|all]
+  python tools/bench_train.py --workload lstm_multi --models 9 --batch 32
 """
 
 from __future__ import annotations
@@ -101,6 +105,90 @@ def bench_lstm_train(nsym=32, T=1_000_000, seq=60, batch=16_384,
     }
 
 
+def bench_lstm_multi(n_models=9, batch=32, T=20_000, seq=60, steps=20,
+                     warmup=3, repeats=3, seed=0):
+    """M per-symbol predictors, per-model batch `batch`, full train steps
+    (fwd + bwd + Adam) two ways on the same resident windows:
+      stacked  one StackedLSTMPricePredictor, one Adam
+      serial   M LSTMPricePredictors with M Adams, one after another
+    `repeats` alternating timed runs of each; medians and max-min spread
+    of aggregate windows/s."""
+    import statistics
+
+    from ai_crypto_trader_amd.data.synthetic import (
+        candles_chl_v, generate_ohlcv,
+    )
+    from ai_crypto_trader_amd.models.lstm import LSTMPricePredictor
+    from ai_crypto_trader_amd.models.lstm_multi import (
+        StackedLSTMPricePredictor,
+    )
+
+    M = n_models
+    candles = torch.from_numpy(
+        candles_chl_v(generate_ohlcv(T, M, seed=seed))).cuda()
+    feats = build_features_gpu(candles)            # (M, T, 9) resident
+    close = candles[..., 0]
+    target = torch.zeros_like(close)
+    target[:, :-1] = (close[:, 1:] / close[:, :-1] - 1.0) * 100.0
+
+    torch.manual_seed(seed)
+    singles = [LSTMPricePredictor(9, seq).cuda() for _ in range(M)]
+    stacked = StackedLSTMPricePredictor.from_models(singles)
+    opt_stacked = torch.optim.Adam(stacked.parameters(), lr=1e-3)
+    opts = [torch.optim.Adam(m.parameters(), lr=1e-3) for m in singles]
+    g = torch.Generator(device="cuda").manual_seed(seed)
+    rows = torch.arange(M, device="cuda")[:, None]
+    ar = torch.arange(seq, device="cuda")
+
+    def sample_batch():
+        t0 = torch.randint(0, T - seq - 1, (M, batch), device="cuda",
+                           generator=g)
+        x = feats[rows[:, :, None], t0[:, :, None] + ar]   # (M, B, seq, 9)
+        y = target[rows, t0 + seq]                         # (M, B)
+        return x, y
+
+    def step_stacked():
+        x, y = sample_batch()
+        opt_stacked.zero_grad(set_to_none=True)
+        ((stacked(x) - y) ** 2).mean(dim=1).sum().backward()
+        opt_stacked.step()
+
+    def step_serial():
+        x, y = sample_batch()
+        for m in range(M):
+            opts[m].zero_grad(set_to_none=True)
+            ((singles[m](x[m]) - y[m]) ** 2).mean().backward()
+            opts[m].step()
+
+    def timed(step):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(steps):
+            step()
+        torch.cuda.synchronize()
+        return M * batch * steps / (time.perf_counter() - t0)
+
+    for _ in range(warmup):
+        step_stacked()
+        step_serial()
+    runs = {"stacked": [], "serial": []}
+    for _ in range(repeats):
+        runs["stacked"].append(timed(step_stacked))
+        runs["serial"].append(timed(step_serial))
+    med = {k: statistics.median(v) for k, v in runs.items()}
+    return {
+        "workload": "lstm_multi_train",
+        "windows_per_sec": med,
+        "spread_windows_per_sec": {k: max(v) - min(v)
+                                   for k, v in runs.items()},
+        "runs_windows_per_sec": runs,
+        "ms_per_step": {k: M * batch / v * 1e3 for k, v in med.items()},
+        "stacked_over_serial": med["stacked"] / med["serial"],
+        "config": {"models": M, "batch": batch, "seq": seq, "T": T,
+                   "steps": steps, "warmup": warmup, "repeats": repeats},
+    }
+
+
 def bench_ppo(n_envs=256, horizon=128, steps=6, warmup=2, seed=0,
               use_graph=False):
     from ai_crypto_trader_amd.data.synthetic import (
@@ -137,11 +225,20 @@ def bench_ppo(n_envs=256, horizon=128, steps=6, warmup=2, seed=0,
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--workload", default="all",
-                    choices=["all", "lstm", "ppo"])
+                    choices=["all", "lstm", "ppo", "lstm_multi"])
+    ap.add_argument("--models", type=int, default=9,
+                    help="lstm_multi: number of per-symbol models")
+    ap.add_argument("--batch", type=int, default=32,
+                    help="lstm_multi: per-model batch size")
+    ap.add_argument("--steps", type=int, default=20,
+                    help="lstm_multi: timed steps per run")
     args = ap.parse_args()
     assert torch.cuda.is_available()
     if args.workload in ("all", "lstm"):
         print(json.dumps(bench_lstm_train()), flush=True)
+    if args.workload == "lstm_multi":
+        print(json.dumps(bench_lstm_multi(args.models, args.batch,
+                                          steps=args.steps)), flush=True)
     if args.workload in ("all", "ppo"):
         print(json.dumps(bench_ppo()), flush=True)
         print(json.dumps(bench_ppo(use_graph=True)), flush=True)
