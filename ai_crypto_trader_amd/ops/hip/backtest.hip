@@ -10,11 +10,18 @@
 //     at pop=1024 x 64 sym x 16 segments: wave-level latency hiding beats
 //     in-lane ILP here because both chains stall on the same LDS
 //     broadcast + f64 sequence.
-//   - candle tiles staged in LDS with a MAX_WIN-candle HALO: close history
-//     is shared by every lane of the block, so the Bollinger "ring buffer"
-//     is just a broadcast read of close[t-W] from the halo tile — no
-//     per-lane LDS state at all (v1 used 32 KB/block of per-lane rings and
-//     was LDS-occupancy-bound at 4 waves/SIMD)
+//   - candle tiles staged in LDS with a 64-candle HALO: close history is
+//     shared by every lane of the block, so the Bollinger "ring buffer"
+//     is just a read of close[t-W] from the halo tile — no per-lane LDS
+//     state at all (v1 used 32 KB/block of per-lane rings and was
+//     LDS-occupancy-bound at 4 waves/SIMD)
+//   - Bollinger {mean, std} depend on the strategy only through its
+//     window length, an integer in [2, 32], so a block computes them once
+//     per candle and window instead of once per lane (up to 8x redundant
+//     f64 + sqrt before): per 32-candle sub-tile, 31 lanes of wave 0 (one
+//     per window) march the f64 rolling sums into an LDS table
+//     [candle][window], then all 256 lanes convert its slots to
+//     {mean, std} in place, and every lane reads its window's slot
 //   - EMA/MACD/Wilder-RSI are O(1) register recurrences per candle
 //   - the position state machine (SL/TP/trailing/vote exits — semantics of
 //     trade_executor_service.py:55-399 + binance_ml_strategy.py:489-543)
@@ -53,15 +60,14 @@ struct BtState {
         acc.init(initial_equity);
     }
 
-    template <bool SKIP_BB>
+    // `ms` = {mean, std} of this lane's Bollinger window at candle t
     __device__ void step(int t, float close, float high, float low,
-                         float oldc, float change, float4 sv)
+                         float change, float2 ms, float4 sv)
     {
 #pragma clang fp contract(off)           // match the numpy f32 reference
         // --- 1+2. indicators, votes ----------------------------------
-        const int net = v.template step<SKIP_BB>(
-            t, close, change, oldc, (double)close * (double)close,
-            (double)oldc * (double)oldc, sv);
+        const int net =
+            v.count(t, close, v.recur(t, close, change), ms, sv);
 
         // --- 3. position management ----------------------------------
         if (in_pos) {
@@ -102,6 +108,34 @@ struct BtState {
     }
 };
 
+// Candles per fill of the Bollinger table. 32 candles x 32 window slots
+// x 16 B = 16 KB: with the staging, 27 KB per block, so the five blocks
+// per CU that the VGPR budget allows also fit its LDS.
+#define BT_BBSUB 32
+static_assert(BT_TILE % BT_BBSUB == 0, "sub-tiles must tile the tile");
+static_assert(BT_BLOCK % BT_MAXWIN == 0 && BT_BBSUB <= BT_BLOCK &&
+                  (BT_MAXWIN & (BT_MAXWIN - 1)) == 0,
+              "a lane converts slots of one window only");
+// The table leaves out the early-window divisor (t + 1 < w): it only
+// exists below MAX_WIN, and no vote is taken before WARMUP, so those
+// entries are never consumed — the sums themselves advance from t = 0.
+static_assert(BT_MAXWIN <= BT_WARMUP, "early-window entries are unused");
+
+// a table slot holds either the f64 sums {sum, sum2} of (candle, window)
+// or, once converted, {mean, std} in its first 8 bytes
+__device__ inline float4 bt_pack_sums(double a, double b)
+{
+    return make_float4(__int_as_float(__double2loint(a)),
+                       __int_as_float(__double2hiint(a)),
+                       __int_as_float(__double2loint(b)),
+                       __int_as_float(__double2hiint(b)));
+}
+
+__device__ inline double bt_unpack_sum(float lo, float hi)
+{
+    return __hiloint2double(__float_as_int(hi), __float_as_int(lo));
+}
+
 template <bool HAS_RESNAP>
 // second arg: min resident blocks/CU — pins the allocation at <=102
 // VGPR so 5 waves/SIMD stay resident (the resnap addition had silently
@@ -115,8 +149,14 @@ __global__ void __launch_bounds__(BT_BLOCK, 5) backtest_kernel(
 {
 #pragma clang fp contract(off)           // match the numpy f32 reference
     __shared__ float chist[BT_SPAN];     // close history incl. halo
+    __shared__ double csq[BT_SPAN];      // (double)close^2, same span
     __shared__ float hl[BT_SPAN][2];     // high, low
     __shared__ float4 sh_vote[BT_TILE];  // bt_shared_votes() per candle
+    // Bollinger table [sub-tile candle][window - 2]; slot 31 is padding
+    __shared__ float4 bbtab[BT_BBSUB * BT_MAXWIN];
+    // per window slot: the rolling sums between sub-tiles, and 1/w
+    __shared__ double sh_sum[BT_MAXWIN], sh_sum2[BT_MAXWIN];
+    __shared__ double sh_invw[BT_MAXWIN];
 
     int sym, chunk;
     bt_block_map(blockIdx.x, nsym, chunks_per_sym, sym, chunk);
@@ -126,44 +166,100 @@ __global__ void __launch_bounds__(BT_BLOCK, 5) backtest_kernel(
 
     BtState st;
     st.load(pop + (long)(act ? p : 0) * BT_NPARAM, initial_equity);
+    const float4* my_bb = bbtab + (st.v.bb_w - 2);
+
+    // The scan lanes: lane j < 31 of wave 0 owns window j + 2, whatever
+    // strategies the block holds, active or not. Its sums live in LDS
+    // between sub-tiles, so no lane carries f64 state through the candle
+    // loop.
+    const int scan_w = tid + 2;
+    const bool is_scan = scan_w <= BT_MAXWIN;
+    if (tid < BT_MAXWIN) {
+        BollState b;
+        b.init(scan_w);
+        sh_sum[tid] = b.sum;
+        sh_sum2[tid] = b.sum2;
+        sh_invw[tid] = b.inv_w;
+    }
+    if (tid < BT_BBSUB)                  // the padding slots: defined bits
+        bbtab[tid * BT_MAXWIN + BT_MAXWIN - 1] =
+            make_float4(0.0f, 0.0f, 0.0f, 0.0f);
 
     float prev_close = 0.f;
     const float4* sym_candles =
         reinterpret_cast<const float4*>(candles + (long)sym * T * 4);
 
     for (int t0 = 0; t0 < T; t0 += BT_TILE) {
-        bt_stage_tile(sym_candles, t0, T, chist, hl, nullptr);
+        bt_stage_tile(sym_candles, t0, T, chist, hl, csq);
         const int tend = min(BT_TILE, T - t0);
         // BB resnap at RESNAP-aligned tiles (engine_cpu.py lockstep):
-        // window closes for candle t0 are chist[BT_HALO - j], j < bb_w.
+        // window closes for candle t0 are chist[BT_HALO - j], j < w; the
+        // resnap candle itself then takes no increment.
         const bool resnap_tile = HAS_RESNAP && (t0 > 0) &&
                                  ((t0 & (BT_RESNAP - 1)) == 0);
-        if (resnap_tile) st.v.resnap(&chist[BT_HALO]);
-        bt_shared_votes(t0, tend, chist, hl, sh_vote);
-        __syncthreads();
-        int tt0 = 0;
-        if (resnap_tile) {
-            // peeled resnap candle: BB increment skipped (template
-            // flag -> zero cost in the steady-state loop below)
-            const float close = chist[BT_HALO];
-            st.template step<true>(t0, close, hl[BT_HALO][0],
-                                   hl[BT_HALO][1],
-                                   chist[BT_HALO - st.v.bb_w],
-                                   close - prev_close, sh_vote[0]);
-            prev_close = close;
-            tt0 = 1;
+        if (resnap_tile && is_scan) {
+            BollState b;
+            b.resnap(scan_w, &chist[BT_HALO]);
+            sh_sum[tid] = b.sum;
+            sh_sum2[tid] = b.sum2;
         }
-        for (int tt = tt0; tt < tend; ++tt) {
-            const int t = t0 + tt;
-            const float close = chist[tt + BT_HALO];
-            const float high = hl[tt + BT_HALO][0];
-            const float low = hl[tt + BT_HALO][1];
-            const float change = (t == 0) ? 0.0f : close - prev_close;
-            const float4 sv = sh_vote[tt];   // b128 broadcast
-            st.template step<false>(t, close, high, low,
-                                    chist[tt + BT_HALO - st.v.bb_w],
-                                    change, sv);
-            prev_close = close;
+        bt_shared_votes(t0, tend, chist, hl, sh_vote);
+        for (int s0 = 0; s0 < tend; s0 += BT_BBSUB) {
+            const int send = min(s0 + BT_BBSUB, tend);
+            // the previous sub-tile's readers are done with the table
+            // (s0 == 0: bt_stage_tile's barriers already say so)
+            if (s0 > 0) __syncthreads();
+            // phase A, scan lanes only: the sums are an inexact, order-
+            // dependent chain, so they march sequentially from candle 0 —
+            // but nothing else does; a slot gets the sums as of its candle
+            if (is_scan) {
+                BollState b;
+                b.sum = sh_sum[tid];
+                b.sum2 = sh_sum2[tid];
+#pragma unroll 4
+                for (int tt = s0; tt < send; ++tt) {
+                    const int i = tt + BT_HALO;
+                    if (!(resnap_tile && tt == 0))
+                        b.advance(chist[i], chist[i - scan_w], csq[i],
+                                  csq[i - scan_w]);
+                    bbtab[(tt - s0) * BT_MAXWIN + tid] =
+                        bt_pack_sums(b.sum, b.sum2);
+                }
+                sh_sum[tid] = b.sum;
+                sh_sum2[tid] = b.sum2;
+            }
+            __syncthreads();
+            // phase B, the whole block: sums -> {mean, std} in place, the
+            // f64 multiplies and the sqrt spread over all lanes. A lane's
+            // slots all belong to one window (BT_BLOCK % BT_MAXWIN == 0).
+            {
+                BollState b;
+                b.inv_w = sh_invw[tid & (BT_MAXWIN - 1)];
+                for (int e = tid; e < (send - s0) * BT_MAXWIN;
+                     e += BT_BLOCK) {
+                    const float4 v = bbtab[e];
+                    b.sum = bt_unpack_sum(v.x, v.y);
+                    b.sum2 = bt_unpack_sum(v.z, v.w);
+                    const float2 ms = b.stats<false>(0, 0);
+                    bbtab[e].x = ms.x;
+                    bbtab[e].y = ms.y;
+                }
+            }
+            __syncthreads();             // table (and sh_vote) visible
+            for (int tt = s0; tt < send; ++tt) {
+                const int t = t0 + tt;
+                const float close = chist[tt + BT_HALO];
+                const float high = hl[tt + BT_HALO][0];
+                const float low = hl[tt + BT_HALO][1];
+                const float change = (t == 0) ? 0.0f : close - prev_close;
+                const float4 sv = sh_vote[tt];   // b128 broadcast
+                // b64 per lane: equal windows broadcast, distinct windows
+                // sit 16 B apart (w and w + 16 share banks: 2-way at most)
+                const float4* e = &my_bb[(tt - s0) * BT_MAXWIN];
+                st.step(t, close, high, low, change,
+                        make_float2(e->x, e->y), sv);
+                prev_close = close;
+            }
         }
     }
 
@@ -177,8 +273,8 @@ extern "C" void launch_backtest(const float* candles, const float* pop,
                                 float* metrics, int nsym, int T, int P,
                                 float initial_equity, hipStream_t stream) {
     // histories short enough never to cross a RESNAP boundary run the
-    // resnap-free instantiation: identical codegen (96 VGPR, 5 waves/
-    // SIMD) to a kernel without the feature — the seg-64 headline path
+    // resnap-free instantiation: the same codegen as a kernel without
+    // the feature — the seg-64 headline path
     const int chunks = (P + BT_BLOCK - 1) / BT_BLOCK;
     auto k = T > BT_RESNAP ? backtest_kernel<true> : backtest_kernel<false>;
     hipLaunchKernelGGL(k, dim3(nsym * chunks), dim3(BT_BLOCK), 0, stream,

@@ -19,6 +19,71 @@
 // chunked launches; ops/backtest.py sizes the carry buffer from it
 #define BT_NSTATE 18
 
+// Rolling Bollinger sums of ONE window length w over one close stream,
+// and the {mean, std} they give. Nothing here depends on a strategy
+// except through w, an integer in [2, BT_MAXWIN]: a kernel may carry one
+// per lane (VoteState::step) or one per window for a whole block
+// (backtest.hip's table).
+struct BollState {
+    double sum, sum2, inv_w;          // f64 sums: f32 drifts + cancels
+
+    __device__ void init(int w)
+    {
+        sum = sum2 = 0.0;
+        inv_w = 1.0 / (double)w;
+    }
+
+    // Drift-free resnap (strategy.py RESNAP): recompute the window sums
+    // directly, oldest->newest, from the close history. `hist` points at
+    // close[t] (the resnap candle itself, j = 0 term).
+    // (noinline was tried here: 86 VGPR/no spills but the call
+    // inside the tile loop cost 25% — inlined + launch-bounds wins)
+    __device__ void resnap(int w, const float* __restrict__ hist)
+    {
+#pragma clang fp contract(off)
+        double s = 0.0, s2 = 0.0;
+        for (int j = BT_MAXWIN - 1; j >= 0; --j) {
+            if (j < w) {
+                double c = (double)hist[-j];
+                s += c;
+                s2 += c * c;
+            }
+        }
+        sum = s;
+        sum2 = s2;
+    }
+
+    // slide the window one candle: `oldc` is close[t - w], csq_* are
+    // (double)close^2 and (double)oldc^2
+    __device__ void advance(float close, float oldc, double csq_new,
+                            double csq_old)
+    {
+#pragma clang fp contract(off)
+        double old = (double)oldc;
+        double c64 = (double)close;
+        sum += c64 - old;
+        sum2 += csq_new - csq_old;
+    }
+
+    // {mean, std} of the window ending at candle t. EARLY = false drops
+    // the early-window divisor: a caller that never consumes the entries
+    // below t = MAX_WIN gets the same bits everywhere else without
+    // carrying the f64 reciprocal.
+    template <bool EARLY = true>
+    __device__ float2 stats(int t, int w) const
+    {
+#pragma clang fp contract(off)
+        double inv_cnt = inv_w;
+        // the early-window divisor only exists in the very first tile
+        // (t < MAX_WIN <= 32 < BT_TILE): uniformly skipped t>=32
+        if (EARLY && t < BT_MAXWIN && t + 1 < w)
+            inv_cnt = 1.0 / (t + 1.0);
+        double mean64 = sum * inv_cnt;
+        double var64 = fmax(sum2 * inv_cnt - mean64 * mean64, 0.0);
+        return make_float2((float)mean64, sqrtf((float)var64));
+    }
+};
+
 // decoded indicator/vote parameters + recurrence state of one strategy
 struct VoteState {
     float inv_rsi_p, rsi_os, rsi_ob;
@@ -30,7 +95,7 @@ struct VoteState {
 
     float ema_f, ema_s, sig;
     float avg_gain, avg_loss;
-    double bb_sum, bb_sum2, inv_w;    // f64 sums: f32 drifts + cancels
+    BollState bb;
 
     __device__ void load(const float* __restrict__ pr)
     {
@@ -47,29 +112,13 @@ struct VoteState {
         will_ob = stoch_ob - 100.0f;
         ema_f = ema_s = sig = 0.f;
         avg_gain = avg_loss = 0.f;
-        bb_sum = bb_sum2 = 0.0;
-        inv_w = 1.0 / (double)bb_w;
+        bb.init(bb_w);
     }
 
-    // Drift-free Bollinger resnap (strategy.py RESNAP): recompute the
-    // window sums directly, oldest->newest, from the close history.
-    // `hist` points at close[t] (the resnap candle itself, j = 0 term).
-    // (noinline was tried here: 86 VGPR/no spills but the call
-    // inside the tile loop cost 25% — inlined + launch-bounds wins)
+    // Bollinger resnap of this strategy's own window (see BollState)
     __device__ void resnap(const float* __restrict__ hist)
     {
-#pragma clang fp contract(off)
-        double s = 0.0, s2 = 0.0;
-        const int w = bb_w;
-        for (int j = BT_MAXWIN - 1; j >= 0; --j) {
-            if (j < w) {
-                double c = (double)hist[-j];
-                s += c;
-                s2 += c * c;
-            }
-        }
-        bb_sum = s;
-        bb_sum2 = s2;
+        bb.resnap(bb_w, hist);
     }
 
     // warm-tail march: the same f32 recurrence ops as step(), minus
@@ -87,16 +136,14 @@ struct VoteState {
         avg_loss += (loss - avg_loss) * inv_rsi_p;
     }
 
-    // One candle: indicators + the 6-indicator TradingSignal vote count;
-    // returns net = buys - sells (0 before WARMUP). `oldc` is
-    // close[t - bb_w]; csq_new / csq_old are (double)close^2 and
-    // (double)oldc^2, passed in so a caller may share them through LDS.
-    // SKIP_BB is a compile-time flag (a resnap() just replaced the sums
-    // for this candle) so the steady-state loop carries no per-candle
-    // branch — the resnap candle is peeled at the call site.
-    template <bool SKIP_BB>
-    __device__ int step(int t, float close, float change, float oldc,
-                        double csq_new, double csq_old, float4 sv)
+    // step() in three parts, so a kernel may take the Bollinger part
+    // from somewhere else (backtest.hip: a block-shared table).
+    //
+    // Part 1, the O(1) register recurrences of one candle: EMA/MACD and
+    // Wilder RSI, as the numerators/denominators the votes compare.
+    struct Osc { float macd_hist, rsi_num, rsi_den; };
+
+    __device__ Osc recur(int t, float close, float change)
     {
 #pragma clang fp contract(off)           // match the numpy f32 reference
         if (t == 0) { ema_f = close; ema_s = close; }
@@ -106,7 +153,8 @@ struct VoteState {
         }
         float macd = ema_f - ema_s;
         sig += a_sig * (macd - sig);
-        float macd_hist = macd - sig;
+        Osc o;
+        o.macd_hist = macd - sig;
 
         float gain = fmaxf(change, 0.0f);
         float loss = fmaxf(-change, 0.0f);
@@ -114,48 +162,56 @@ struct VoteState {
         avg_loss += (loss - avg_loss) * inv_rsi_p;
         // division-free RSI votes (engine_cpu.py): rsi<thr <=>
         // 100*ag < thr*(ag+al')
-        float rsi_num = 100.0f * avg_gain;
-        float rsi_den = avg_gain + fmaxf(avg_loss, BT_EPS);
+        o.rsi_num = 100.0f * avg_gain;
+        o.rsi_den = avg_gain + fmaxf(avg_loss, BT_EPS);
+        return o;
+    }
 
-        // Bollinger: close[t - W] comes from the shared halo tile
-        // (== the zero-initialized per-lane ring of engine_cpu.py)
-        if (!SKIP_BB) {
-            double old = (double)oldc;
-            double c64 = (double)close;
-            bb_sum += c64 - old;
-            bb_sum2 += csq_new - csq_old;
-        }
-        double inv_cnt = inv_w;
-        // the early-window divisor only exists in the very first tile
-        // (t < MAX_WIN <= 32 < BT_TILE): uniformly skipped t>=32
-        if (t < BT_MAXWIN && t + 1 < bb_w)
-            inv_cnt = 1.0 / (t + 1.0);
-        double mean64 = bb_sum * inv_cnt;
-        double var64 = fmax(bb_sum2 * inv_cnt - mean64 * mean64, 0.0);
-        float mean = (float)mean64;
-        float std_ = sqrtf((float)var64);
-        float band = bb_k * std_;
+    // Part 3, the 6-indicator TradingSignal vote count: net = buys -
+    // sells (0 before WARMUP). `ms` is BollState::stats() of this
+    // strategy's window at candle t.
+    __device__ int count(int t, float close, Osc o, float2 ms,
+                         float4 sv) const
+    {
+#pragma clang fp contract(off)           // match the numpy f32 reference
+        float band = bb_k * ms.y;
         // division-free BB votes (engine_cpu.py): pos<thr <=> num<thr*den
-        float bb_num = close - (mean - band);
+        float bb_num = close - (ms.x - band);
         float bb_den = fmaxf(2.0f * band, BT_EPS);
 
         int net = 0;
         if (t >= BT_WARMUP) {
-            int buy = (rsi_num < rsi_os * rsi_den) +
-                      (macd_hist > 0.0f) +
+            int buy = (o.rsi_num < rsi_os * o.rsi_den) +
+                      (o.macd_hist > 0.0f) +
                       (bb_num < bb_bth * bb_den) +
                       (sv.x < stoch_os * sv.z) +
-                      (sv.y < will_os * sv.z) +
-                      (sv.w > 0.0f);
-            int sell = (rsi_num > rsi_ob * rsi_den) +
-                       (macd_hist < 0.0f) +
+                      (sv.y < will_os * sv.z);
+            int sell = (o.rsi_num > rsi_ob * o.rsi_den) +
+                       (o.macd_hist < 0.0f) +
                        (bb_num > bb_sth * bb_den) +
                        (sv.x > stoch_ob * sv.z) +
-                       (sv.y > will_ob * sv.z) +
-                       (sv.w < 0.0f);
-            net = buy - sell;
+                       (sv.y > will_ob * sv.z);
+            // sixth vote: the shared trend, already +1 / -1 / 0
+            net = buy - sell + __float_as_int(sv.w);
         }
         return net;
+    }
+
+    // One candle with a per-lane Bollinger window (part 2 in between):
+    // `oldc` is close[t - bb_w]; csq_new / csq_old are (double)close^2
+    // and (double)oldc^2, passed in so a caller may share them through
+    // LDS. SKIP_BB is a compile-time flag (a resnap() just replaced the
+    // sums for this candle) so the steady-state loop carries no
+    // per-candle branch — the resnap candle is peeled at the call site.
+    template <bool SKIP_BB>
+    __device__ int step(int t, float close, float change, float oldc,
+                        double csq_new, double csq_old, float4 sv)
+    {
+        const Osc o = recur(t, close, change);
+        // close[t - W] comes from the shared halo tile (== the
+        // zero-initialized per-lane ring of engine_cpu.py)
+        if (!SKIP_BB) bb.advance(close, oldc, csq_new, csq_old);
+        return count(t, close, o, bb.stats(t, bb_w), sv);
     }
 };
 
@@ -186,7 +242,8 @@ __device__ inline void bt_stage_tile(
 // one thread per candle (strategy.py step-1 spec: every lane of a symbol
 // shares them), packed {st_num, wl_num, srange, trend}: st_num =
 // 100*(close-lmin14), wl_num = -100*(hmax14-close), srange =
-// max(hmax-lmin, eps), trend = +-1/0 from close vs sma20/50 — so the
+// max(hmax-lmin, eps), trend = the trend vote's buy - sell (+-1/0 from
+// close vs sma20/50) as an int's bits, which a lane just adds — so the
 // lane loop needs one b128 broadcast read per candle. Finite windows over
 // the staged halo: exact wherever the tile starts. The caller's barrier
 // publishes sh_vote.
@@ -214,10 +271,9 @@ __device__ inline void bt_shared_votes(
     double s50 = 0.0;
     for (int j = 0; j < L50; ++j) s50 += (double)chist[base - j];
     const float sma50 = (float)(s50 / (double)L50);
-    const float trend = (cl > sma20 && sma20 > sma50) ? 1.0f
-                        : ((cl < sma20 && sma20 < sma50) ? -1.0f
-                                                         : 0.0f);
+    const int trend = (cl > sma20 && sma20 > sma50) ? 1
+                      : ((cl < sma20 && sma20 < sma50) ? -1 : 0);
     sh_vote[tid] = make_float4(
         100.0f * (cl - lmin), -100.0f * (hmax - cl),
-        fmaxf(hmax - lmin, BT_EPS), trend);
+        fmaxf(hmax - lmin, BT_EPS), __int_as_float(trend));
 }
