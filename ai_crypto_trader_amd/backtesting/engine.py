@@ -26,6 +26,7 @@ from ..backtesting.strategy import (
 )
 from ..ops import gpu_available
 from .families import FAMILIES
+from .ledger import DEFAULT_MAX_TRADES
 from .data_manager import HistoricalDataManager
 
 ANNUAL_CANDLES = 525_600.0      # 1m bars
@@ -112,12 +113,21 @@ class BacktestEngine:
         self.device = device
         self.results_dir = Path(data_dir) / "results"
         self.results_dir.mkdir(parents=True, exist_ok=True)
+        self.last_saved: Path | None = None      # newest results JSON
 
     # --- single run ------------------------------------------------------
     def run_backtest(self, symbol: str, strategy: str = "default",
                      interval: str = "1m", n_candles: int = 10_000,
                      params: dict | None = None,
-                     record_equity: bool = False) -> dict:
+                     record_equity: bool = False,
+                     record_trades: bool = False,
+                     max_trades: int = DEFAULT_MAX_TRADES,
+                     equity_stride: int = 1) -> dict:
+        """record_trades (vote machine only) adds the trade ledger to the
+        stats: `trades` (backtesting/ledger.py records as dicts, at most
+        max_trades), `n_open`, and the trade-derived numbers of
+        evaluation.calculate_metrics / calculate_advanced_metrics.
+        equity_stride thins the recorded equity curve (vote machine)."""
         df = self.dm.load_market_data(symbol, interval,
                                       n_candles=n_candles)
         candles = self.dm.to_chlv(df.iloc[:n_candles])
@@ -131,10 +141,20 @@ class BacktestEngine:
                 preset.update(params)
             vec = clip_params(dict_to_params(preset)[None])
             to_dict = params_to_dict
+        if fam is not None and record_trades:
+            raise ValueError(
+                f"no trade ledger for the {strategy!r} family: its fills "
+                "are per level / per order, not one position at a time")
+        ledger = None
         t0 = time.perf_counter()
-        out = self._run(candles, vec, record_equity, fam)
+        if fam is None and (record_trades or record_equity):
+            ledger = self._run_ledger(candles, vec, max_trades,
+                                      equity_stride)
+            metrics = ledger.metrics
+        else:
+            out = self._run(candles, vec, record_equity, fam)
+            metrics = out[0] if record_equity else out
         elapsed = time.perf_counter() - t0
-        metrics = out[0] if record_equity else out
         T = candles.shape[1]
         stats = metrics_to_stats(metrics[0, 0], T, interval)
         stats.update({
@@ -143,10 +163,59 @@ class BacktestEngine:
             "candles_per_sec": T / max(elapsed, 1e-9),
             "params": to_dict(vec[0]),
         })
-        if record_equity:
+        if ledger is not None:
+            if record_equity:
+                stats["equity_curve"] = ledger.equity[0, 0].tolist()
+                stats["equity_stride"] = ledger.equity_stride
+            if record_trades:
+                stats.update(self._trade_stats(ledger))
+        elif record_equity:
             stats["equity_curve"] = out[1][0, 0].tolist()
         self._save(stats)
         return stats
+
+    def _run_ledger(self, candles: np.ndarray, pop: np.ndarray,
+                    max_trades: int, equity_stride: int):
+        """Vote machine with the trade ledger: the HIP ledger kernel on a
+        GPU, its numpy twin on CPU — the same `Ledger`, as numpy."""
+        if self.device.startswith("cuda"):
+            import torch
+
+            from ..ops.backtest import run_backtest_ledger_gpu
+            led = run_backtest_ledger_gpu(
+                torch.from_numpy(candles).to(self.device),
+                torch.from_numpy(pop).to(self.device),
+                max_trades=max_trades, equity_stride=equity_stride)
+            torch.cuda.synchronize()
+            return led.numpy()
+        return run_backtest_cpu(candles, pop, record_trades=True,
+                                max_trades=max_trades,
+                                equity_stride=equity_stride)
+
+    @staticmethod
+    def _trade_stats(ledger) -> dict:
+        """Lane (0, 0)'s records and what only a trade list can say:
+        avg win/loss, streaks, per-trade expectancy."""
+        from .evaluation import (
+            calculate_advanced_metrics, calculate_metrics,
+        )
+        trades = ledger.trades(0, 0)
+        closed = [t for t in trades if t["reason"] != "open"]
+        out = {
+            "trades": trades,
+            "n_open": len(trades) - len(closed),
+            "n_records": int(ledger.n_records[0, 0]),
+            "avg_win": 0.0, "avg_loss": 0.0, "max_win_streak": 0,
+            "max_loss_streak": 0, "expectancy": 0.0,
+        }
+        if closed:
+            eq = ledger.equity[0, 0]
+            basic = calculate_metrics(eq, closed)
+            adv = calculate_advanced_metrics(eq, closed)
+            out.update({k: basic[k] for k in ("avg_win", "avg_loss")})
+            out.update({k: adv[k] for k in (
+                "max_win_streak", "max_loss_streak", "expectancy")})
+        return out
 
     def _run(self, candles: np.ndarray, pop: np.ndarray,
              record_equity: bool = False, fam=None):
@@ -181,9 +250,12 @@ class BacktestEngine:
     # --- GA parameter optimization over the GPU kernel -------------------
     def optimize(self, symbol: str, pop_size: int = 256,
                  generations: int = 10, n_candles: int = 20_000,
-                 seed: int = 0, strategy: str = "vote") -> dict:
+                 seed: int = 0, strategy: str = "vote",
+                 record_trades: bool = False) -> dict:
         """strategy: "vote" (the vote machine) or a family name ("grid",
-        "dca") — the GA then searches that family's parameter space."""
+        "dca") — the GA then searches that family's parameter space.
+        record_trades: the final run of the winner keeps its trade ledger
+        (vote machine only)."""
         from .ga_engine import GAEngine
 
         df = self.dm.load_market_data(symbol, n_candles=n_candles)
@@ -206,7 +278,8 @@ class BacktestEngine:
         else:
             stats = self.run_backtest(symbol, "optimized",
                                       params=params_to_dict(best),
-                                      n_candles=n_candles)
+                                      n_candles=n_candles,
+                                      record_trades=record_trades)
         stats["optimize"] = {
             "pop_size": pop_size, "generations": generations,
             "best_fitness": fit, "fitness_history": history,
@@ -219,7 +292,8 @@ class BacktestEngine:
         name = (f"{stats['symbol']}_{stats['strategy']}_"
                 f"{int(time.time())}.json")
         slim = {k: v for k, v in stats.items() if k != "equity_curve"}
-        with open(self.results_dir / name, "w") as f:
+        self.last_saved = self.results_dir / name
+        with open(self.last_saved, "w") as f:
             json.dump(slim, f, indent=2)
 
     def list_results(self) -> list[dict]:

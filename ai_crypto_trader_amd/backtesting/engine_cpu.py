@@ -18,6 +18,9 @@ from __future__ import annotations
 
 import numpy as np
 
+from .ledger import (
+    DEFAULT_MAX_TRADES, FLOAT_FIELDS, INT_FIELDS, Ledger, n_equity_samples,
+)
 from .strategy import FEE, MAX_WIN, NPARAM, RESNAP, WARMUP
 
 NMETRIC = 10
@@ -71,11 +74,19 @@ def run_backtest_cpu(
     initial_equity: float = 1.0,
     record_equity: bool = False,
     record_net: bool = False,
+    record_trades: bool = False,
+    max_trades: int = DEFAULT_MAX_TRADES,
+    equity_stride: int = 1,
 ):
     """Run every param-set against every symbol.
 
     Returns metrics (P, nsym, NMETRIC) f32; optionally the full equity
     curves (P, nsym, T) f32 for plotting/validation.
+
+    record_trades=True returns a `Ledger` (backtesting/ledger.py) instead:
+    the metrics, up to `max_trades` trade records per lane and the equity
+    sampled every `equity_stride` candles — the twin of
+    ops/hip/backtest_ledger.hip.
     """
     f32 = np.float32
     candles = np.asarray(candles, dtype=f32)
@@ -142,6 +153,27 @@ def run_backtest_cpu(
 
     curves = np.empty((L, T), f32) if record_equity else None
     nets = np.empty((L, T), np.int32) if record_net else None
+
+    if record_trades:
+        assert not (record_equity or record_net), \
+            "the ledger carries its own equity samples"
+        assert max_trades >= 1 and equity_stride >= 1
+        n_rec = np.zeros(L, np.int32)
+        rec = {f: np.full((L, max_trades), -1, np.int32)
+               for f in INT_FIELDS}
+        rec.update({f: np.zeros((L, max_trades), f32)
+                    for f in FLOAT_FIELDS})
+        pend_t = np.full(L, -1, np.int32)     # entry candle, open position
+        eq_samples = np.empty((L, n_equity_samples(T, equity_stride)), f32)
+
+        def put_records(idx, **vals):
+            """Append one record to each lane of idx that has room;
+            count it either way (overflow drops the newest)."""
+            keep = idx[n_rec[idx] < max_trades]
+            slot = n_rec[keep]
+            for f, v in vals.items():
+                rec[f][keep, slot] = v[keep] if np.ndim(v) else v
+            n_rec[idx] += 1
 
     close_all = np.ascontiguousarray(candles[:, :, 0])   # (nsym, T)
     high_all = np.ascontiguousarray(candles[:, :, 1])
@@ -260,6 +292,17 @@ def run_backtest_cpu(
 
         proceeds = units * exit_price * (f32(1.0) - f32(FEE))
         pnl = proceeds - entry_cost
+        if record_trades and exiting.any():
+            # a stop that trailing raised above where the entry put it
+            # (the same f32 product as the entry's `stop` below)
+            trailed = stop > entry_price * (f32(1.0) - sl_pct)
+            put_records(
+                np.nonzero(exiting)[0], entry_t=pend_t,
+                exit_t=np.int32(t),
+                reason=np.where(hit_sl, np.where(trailed, 4, 1),
+                                np.where(hit_tp, 2, 3)).astype(np.int32),
+                entry_price=entry_price, exit_price=exit_price,
+                units=units, entry_cost=entry_cost, pnl=pnl)
         cash = np.where(exiting, cash + proceeds, cash)
         n_trades += exiting
         wins += exiting & (pnl > 0)
@@ -279,6 +322,8 @@ def run_backtest_cpu(
         tp = np.where(entering, close * (f32(1.0) + tp_pct), tp)
         peak = np.where(entering, close, peak)
         in_pos = in_pos | entering
+        if record_trades:
+            pend_t = np.where(entering, np.int32(t), pend_t)
 
         # --- 4. mark to market --------------------------------------------
         new_eq = cash + units * close
@@ -290,10 +335,24 @@ def run_backtest_cpu(
         max_dd = np.maximum(max_dd, (max_eq - equity) / max_eq)
         if record_equity:
             curves[:, t] = equity
+        if record_trades and ((t + 1) % equity_stride == 0 or t == T - 1):
+            eq_samples[:, t // equity_stride] = equity
 
     metrics = finalize_metrics(
         T, equity, n_trades, wins, gross_p, gross_l, max_dd, sum_ret, sum_ret2
     ).reshape(P, nsym, NMETRIC)
+    if record_trades:
+        if in_pos.any():                      # still open at T
+            put_records(
+                np.nonzero(in_pos)[0], entry_t=pend_t, exit_t=np.int32(-1),
+                reason=np.int32(0), entry_price=entry_price,
+                exit_price=f32(0.0), units=units, entry_cost=entry_cost,
+                pnl=f32(0.0))
+        return Ledger(
+            metrics, n_rec.reshape(P, nsym),
+            *(rec[f].reshape(P, nsym, max_trades)
+              for f in INT_FIELDS + FLOAT_FIELDS),
+            eq_samples.reshape(P, nsym, -1), int(equity_stride))
     extras = []
     if record_equity:
         extras.append(curves.reshape(P, nsym, T))

@@ -90,9 +90,12 @@ class ResultAnalyzer:
         return p
 
     def trade_analysis(self, stats: dict) -> dict:
-        """(:150-225) trade-level aggregates from the stats dict."""
+        """(:150-225) trade-level aggregates from the stats dict; with a
+        trade ledger (stats["trades"], backtesting/ledger.py) also the
+        per-exit-reason split, durations, avg win/loss and the true
+        per-trade expectancy, over the closed trades."""
         n = stats.get("n_trades", 0)
-        return {
+        out = {
             "n_trades": n,
             "win_rate": stats.get("win_rate", 0.0),
             "profit_factor": stats.get("profit_factor", 0.0),
@@ -100,3 +103,63 @@ class ResultAnalyzer:
                 (stats.get("total_return_pct", 0.0) / n) if n else 0.0,
             "max_drawdown_pct": stats.get("max_drawdown_pct", 0.0),
         }
+        if "trades" not in stats:
+            return out
+        closed = [t for t in stats["trades"] if t["reason"] != "open"]
+        by_reason = {}
+        for t in closed:
+            r = by_reason.setdefault(t["reason"], {"count": 0, "pnl": 0.0})
+            r["count"] += 1
+            r["pnl"] += t["pnl"]
+        pnl = np.asarray([t["pnl"] for t in closed], np.float64)
+        dur = np.asarray([t["duration"] for t in closed], np.float64)
+        wins, losses = pnl[pnl > 0], pnl[pnl <= 0]
+        out.update({
+            "n_closed": len(closed),
+            "n_open": len(stats["trades"]) - len(closed),
+            "by_reason": by_reason,
+            "realized_pnl": float(pnl.sum()),
+            "mean_duration": float(dur.mean()) if len(dur) else 0.0,
+            "median_duration": float(np.median(dur)) if len(dur) else 0.0,
+            "avg_win": float(wins.mean()) if len(wins) else 0.0,
+            "avg_loss": float(losses.mean()) if len(losses) else 0.0,
+            "expectancy": float(pnl.mean()) if len(pnl) else 0.0,
+        })
+        return out
+
+    def plot_trade_analysis(self, stats: dict, fname: str | None = None):
+        """(:150-225) the four trade panels: pnl per trade, win/loss
+        split, duration histogram, pnl by exit reason."""
+        closed = [t for t in stats.get("trades", [])
+                  if t["reason"] != "open"]
+        if not closed:
+            return None
+        import matplotlib
+        matplotlib.use("Agg")
+        import matplotlib.pyplot as plt
+
+        ta = self.trade_analysis(stats)
+        pnl = np.asarray([t["pnl"] for t in closed])
+        fig, ax = plt.subplots(2, 2, figsize=(12, 8))
+        ax[0, 0].bar(np.arange(len(pnl)), pnl,
+                     color=np.where(pnl > 0, "g", "r"))
+        ax[0, 0].set_title("pnl per trade")
+        n_win = int((pnl > 0).sum())
+        ax[0, 1].pie([max(n_win, 1e-9), max(len(pnl) - n_win, 1e-9)],
+                     labels=[f"wins ({n_win})",
+                             f"losses ({len(pnl) - n_win})"],
+                     colors=["g", "r"], autopct="%1.0f%%")
+        ax[0, 1].set_title("win / loss")
+        ax[1, 0].hist([t["duration"] for t in closed], bins=30)
+        ax[1, 0].set_title("trade duration (candles)")
+        reasons = sorted(ta["by_reason"])
+        vals = [ta["by_reason"][r]["pnl"] for r in reasons]
+        ax[1, 1].bar(reasons, vals,
+                     color=["g" if v > 0 else "r" for v in vals])
+        ax[1, 1].set_title("pnl by exit reason")
+        fig.suptitle(f"{stats.get('symbol')} {stats.get('strategy')} — "
+                     f"{len(closed)} trades")
+        p = self.out_dir / (fname or f"{stats.get('symbol')}_trades.png")
+        fig.savefig(p, dpi=80)
+        plt.close(fig)
+        return p

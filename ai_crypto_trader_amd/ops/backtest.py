@@ -11,6 +11,10 @@ import torch
 
 from . import require_hip_ops
 from ..backtesting.engine_cpu import NMETRIC
+from ..backtesting.ledger import (
+    DEFAULT_MAX_TRADES, FIELDS, INT_FIELDS, RECORD_BYTES, Ledger,
+    n_equity_samples,
+)
 from ..backtesting.strategy import (
     MAX_WIN, NPARAM, RESNAP, SHARED_HALO, WARMUP,
 )
@@ -41,6 +45,71 @@ def run_backtest_gpu(
         nsym, T, P, float(initial_equity), stream,
     )
     return metrics
+
+
+def run_backtest_ledger_gpu(
+    candles: torch.Tensor,     # (nsym, T, 4) f32 cuda
+    population: torch.Tensor,  # (P, NPARAM) f32 cuda
+    *,
+    max_trades: int = DEFAULT_MAX_TRADES,
+    equity_stride: int = 1,
+    initial_equity: float = 1.0,
+) -> Ledger:
+    """run_backtest_gpu plus what each lane did (HIP kernel:
+    ops/hip/backtest_ledger.hip): up to `max_trades` trade records per
+    (strategy, symbol) and the equity sampled every `equity_stride`
+    candles, as a `Ledger` of cuda tensors (backtesting/ledger.py has the
+    contract). CPU twin: run_backtest_cpu(record_trades=True), equal bit
+    for bit. Meant for inspecting a few strategies, not a population:
+    the output is P*nsym*(32*max_trades + 4*ceil(T/equity_stride)) bytes.
+    """
+    ops = require_hip_ops()
+    _check_contract(ops)
+    assert candles.is_cuda and population.is_cuda
+    assert candles.dtype == torch.float32
+    assert population.dtype == torch.float32
+    assert candles.dim() == 3 and candles.shape[2] == 4
+    assert population.dim() == 2 and population.shape[1] == NPARAM
+    max_trades, equity_stride = int(max_trades), int(equity_stride)
+    assert max_trades >= 1 and equity_stride >= 1
+    candles = candles.contiguous()
+    population = population.contiguous()
+    nsym, T, _ = candles.shape
+    P = population.shape[0]
+    assert nsym >= 1 and T >= 1 and P >= 1
+    n_samples = n_equity_samples(T, equity_stride)
+    dev = candles.device
+    nbytes = P * nsym * (RECORD_BYTES * max_trades + 4 * n_samples)
+    free, _total = torch.cuda.mem_get_info(dev)
+    assert nbytes <= free, (
+        f"ledger output needs {nbytes / 2**30:.1f} GiB "
+        f"({P} x {nsym} lanes x ({max_trades} records + {n_samples} equity "
+        f"samples)), {free / 2**30:.1f} GiB free: lower max_trades, raise "
+        f"equity_stride or run fewer strategies")
+    metrics = torch.empty((P, nsym, NMETRIC), dtype=torch.float32,
+                          device=dev)
+    n_records = torch.zeros((P, nsym), dtype=torch.int32, device=dev)
+    # lane-major records of 8 32-bit words: three ints, five floats. The
+    # kernel writes whole records only, so unused slots keep this filler:
+    # -1 in the integer fields, 0 in the float fields.
+    words = torch.zeros((P, nsym, max_trades, len(FIELDS)),
+                        dtype=torch.int32, device=dev)
+    words[..., :len(INT_FIELDS)] = -1
+    # time-major with the strategy fastest: a wave's stores coalesce
+    equity = torch.empty((nsym, n_samples, P), dtype=torch.float32,
+                         device=dev)
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    ops.backtest_ledger(
+        candles.data_ptr(), population.data_ptr(), metrics.data_ptr(),
+        n_records.data_ptr(), words.data_ptr(), equity.data_ptr(),
+        nsym, T, P, max_trades, equity_stride, n_samples,
+        float(initial_equity), stream,
+    )
+    fwords = words.view(torch.float32)
+    cols = [words[..., i] if f in INT_FIELDS else fwords[..., i]
+            for i, f in enumerate(FIELDS)]
+    return Ledger(metrics, n_records, *cols, equity.permute(2, 0, 1),
+                  equity_stride)
 
 
 # Flag-bitmap buffers reused across GA generations (16.4 GB at the

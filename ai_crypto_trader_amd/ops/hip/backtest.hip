@@ -29,35 +29,28 @@
 //     operation order, f64 Bollinger sums both sides).
 //
 // The indicator/vote step, tile staging and shared-series precompute are
-// bt_vote.hpp (shared with backtest_tp.hip); the metrics accumulator and
-// the block map are bt_common.hpp (shared with every backtest kernel).
+// bt_vote.hpp (shared with backtest_tp.hip); the position machine is
+// bt_position.hpp (shared with backtest_ledger.hip); the metrics
+// accumulator and the block map are bt_common.hpp (shared with every
+// backtest kernel).
 //
 // Grid: nsym * ceil(P/256) blocks, XCD-affine map keeps the blocks of one
 // symbol on one XCD so their shared candle stream stays in that XCD's L2.
 
-#include "bt_vote.hpp"
+#include "bt_position.hpp"
 
 namespace {
 
-// one strategy's full simulation state: indicators + position + metrics
+// one strategy's full simulation state: indicators + votes (bt_vote.hpp)
+// and position + metrics (bt_position.hpp)
 struct BtState {
     VoteState v;
-    float size_pct, sl_pct, tp_pct, trail_pct, trail_act;
-    float cash, units;
-    bool in_pos;
-    float entry_cost, entry_price;
-    float stop, tp, peak;
-    BtAccum acc;
+    BtPosition pos;
 
     __device__ void load(const float* __restrict__ pr, float initial_equity)
     {
         v.load(pr);
-        size_pct = pr[12]; sl_pct = pr[13]; tp_pct = pr[14];
-        trail_pct = pr[15]; trail_act = pr[16];
-        cash = initial_equity; units = 0.f;
-        in_pos = false;
-        entry_cost = entry_price = stop = tp = peak = 0.f;
-        acc.init(initial_equity);
+        pos.load(pr, initial_equity);
     }
 
     // `ms` = {mean, std} of this lane's Bollinger window at candle t
@@ -68,43 +61,9 @@ struct BtState {
         // --- 1+2. indicators, votes ----------------------------------
         const int net =
             v.count(t, close, v.recur(t, close, change), ms, sv);
-
-        // --- 3. position management ----------------------------------
-        if (in_pos) {
-            peak = fmaxf(peak, high);
-            bool trail_on = (trail_pct > 0.0f) &&
-                            (peak >= entry_price * (1.0f + trail_act));
-            if (trail_on)
-                stop = fmaxf(stop, peak * (1.0f - trail_pct));
-            bool hit_sl = low <= stop;
-            bool hit_tp = !hit_sl && high >= tp;
-            bool hit_sig = !hit_sl && !hit_tp && net <= -v.exit_v;
-            if (hit_sl || hit_tp || hit_sig) {
-                float exit_price = hit_sl ? stop : (hit_tp ? tp : close);
-                float proceeds = units * exit_price * (1.0f - BT_FEE);
-                cash += proceeds;
-                acc.trade(proceeds - entry_cost);
-                units = 0.0f;
-                in_pos = false;
-            }
-        } else if (t >= BT_WARMUP && net >= v.entry_v) {
-            float cost = fminf(size_pct * acc.equity, cash);
-            units = cost * (1.0f - BT_FEE) / close;
-            cash -= cost;
-            entry_cost = cost;
-            entry_price = close;
-            stop = close * (1.0f - sl_pct);
-            tp = close * (1.0f + tp_pct);
-            peak = close;
-            in_pos = true;
-        }
-
-        // --- 4. mark to market ---------------------------------------
-        // flat lanes: new_eq == cash == equity exactly, so r == 0 and
-        // every accumulator is unchanged — skipping is bit-identical
-        // to engine_cpu.py (which computes r = cash/cash - 1 = 0)
-        if (units != 0.0f || cash != acc.equity)
-            acc.mark(cash + units * close);
+        // --- 3+4. position, mark to market; this kernel keeps only the
+        // metrics, so what the candle did (the event) is dropped
+        pos.step(t, net, v.entry_v, v.exit_v, close, high, low);
     }
 };
 
@@ -264,7 +223,7 @@ __global__ void __launch_bounds__(BT_BLOCK, 5) backtest_kernel(
     }
 
     if (act)
-        st.acc.finalize(metrics + ((long)p * nsym + sym) * BT_NMETRIC, T);
+        st.pos.acc.finalize(metrics + ((long)p * nsym + sym) * BT_NMETRIC, T);
 }
 
 }  // namespace

@@ -26,6 +26,9 @@ extern "C" void launch_bt_trades(const float*, const float*,
                                  float*, hipStream_t);
 extern "C" void launch_backtest(const float*, const float*, float*, int, int,
                                 int, float, hipStream_t);
+extern "C" void launch_backtest_ledger(const float*, const float*, float*,
+                                       int*, float*, float*, int, int, int,
+                                       int, int, int, float, hipStream_t);
 extern "C" void launch_ga_evolve(const float*, const float*, const int*,
                                  const float*, float*, int, int, int, float,
                                  float, float, uint64_t, uint64_t,
@@ -127,6 +130,35 @@ PYBIND11_MODULE(_hip_ops, m) {
           },
           py::arg("candles"), py::arg("pop"), py::arg("metrics"),
           py::arg("nsym"), py::arg("T"), py::arg("P"),
+          py::arg("initial_equity"), py::arg("stream"));
+
+    // backtest_ledger.hip: `backtest` plus per-lane trade records
+    // (P, nsym, max_trades, 8 words) and equity samples (nsym, n_samples,
+    // P); the caller pre-fills the record buffers (backtesting/ledger.py)
+    m.def("backtest_ledger",
+          [](uintptr_t candles, uintptr_t pop, uintptr_t metrics,
+             uintptr_t n_records, uintptr_t records, uintptr_t equity,
+             int nsym, int T, int P, int max_trades, int stride,
+             int n_samples, float initial_equity, uintptr_t stream) {
+              // the kernel writes exactly ceil(T / stride) samples per lane
+              if (nsym < 1 || T < 1 || P < 1 || max_trades < 1 ||
+                  stride < 1 || n_samples != (T + stride - 1) / stride)
+                  throw std::invalid_argument(
+                      "backtest_ledger: bad shape arguments");
+              launch_backtest_ledger(
+                  reinterpret_cast<const float*>(candles),
+                  reinterpret_cast<const float*>(pop),
+                  reinterpret_cast<float*>(metrics),
+                  reinterpret_cast<int*>(n_records),
+                  reinterpret_cast<float*>(records),
+                  reinterpret_cast<float*>(equity), nsym, T, P, max_trades,
+                  stride, n_samples, initial_equity, as_stream(stream));
+              check(hipGetLastError(), "backtest_ledger launch");
+          },
+          py::arg("candles"), py::arg("pop"), py::arg("metrics"),
+          py::arg("n_records"), py::arg("records"), py::arg("equity"),
+          py::arg("nsym"), py::arg("T"), py::arg("P"),
+          py::arg("max_trades"), py::arg("stride"), py::arg("n_samples"),
           py::arg("initial_equity"), py::arg("stream"));
 
     m.def("bt_flags",

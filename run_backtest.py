@@ -7,6 +7,7 @@ Examples:
   python run_backtest.py fetch --symbol BTCUSDC --candles 20000
   python run_backtest.py backtest --symbol BTCUSDC --strategy dca_strategy
   python run_backtest.py backtest --symbol BTCUSDC --strategy momentum --plot
+  python run_backtest.py backtest --symbol BTCUSDC --trades --equity-stride 60
   python run_backtest.py optimize --symbol BTCUSDC --pop 256 --generations 10
   python run_backtest.py optimize --symbol BTCUSDC --strategy grid
   python run_backtest.py backtest --symbol BTCUSDC --strategy dca
@@ -17,6 +18,7 @@ Examples:
 from __future__ import annotations
 
 import argparse
+import csv
 import json
 
 from ai_crypto_trader_amd.backtesting.data_manager import (
@@ -26,6 +28,9 @@ from ai_crypto_trader_amd.backtesting.engine import (
     STRATEGY_PRESETS, BacktestEngine,
 )
 from ai_crypto_trader_amd.backtesting.families import FAMILIES
+from ai_crypto_trader_amd.backtesting.ledger import (
+    DEFAULT_MAX_TRADES, FIELDS, REASONS,
+)
 from ai_crypto_trader_amd.backtesting.result_analyzer import ResultAnalyzer
 
 
@@ -53,6 +58,14 @@ def main():
     b.add_argument("--plot", action="store_true")
     b.add_argument("--params", type=str, default=None,
                    help="JSON dict of parameter overrides")
+    b.add_argument("--trades", action="store_true",
+                   help="record the trade ledger (vote machine): print "
+                        "the per-exit-reason table and write a "
+                        "*_trades.csv next to the saved JSON")
+    b.add_argument("--max-trades", type=int, default=DEFAULT_MAX_TRADES,
+                   help="trade records kept (the newest are dropped)")
+    b.add_argument("--equity-stride", type=int, default=1,
+                   help="keep every Nth candle of the equity curve")
 
     o = sub.add_parser("optimize", help="GA parameter search")
     o.add_argument("--symbol", required=True)
@@ -93,13 +106,35 @@ def main():
         params = json.loads(args.params) if args.params else None
         stats = eng.run_backtest(
             args.symbol, args.strategy, args.interval, args.candles,
-            params=params, record_equity=args.plot)
+            params=params, record_equity=args.plot,
+            record_trades=args.trades, max_trades=args.max_trades,
+            equity_stride=args.equity_stride)
+        ra = ResultAnalyzer(f"{args.data_dir}/analysis")
         if args.plot:
-            p = ResultAnalyzer(f"{args.data_dir}/analysis").plot_equity_curve(
-                stats)
+            p = ra.plot_equity_curve(stats)
             print(f"plot -> {p}")
             stats.pop("equity_curve", None)
+            if stats.get("trades"):
+                print(f"trade plot -> {ra.plot_trade_analysis(stats)}")
+        trades = stats.pop("trades", None)
         print(json.dumps(stats, indent=2, default=str))
+        if trades is not None:
+            stats["trades"] = trades
+            ta = ra.trade_analysis(stats)
+            print(f"{'exit reason':<14} {'count':>6} {'pnl':>12}")
+            for r in REASONS[1:]:
+                row = ta["by_reason"].get(r, {"count": 0, "pnl": 0.0})
+                print(f"{r:<14} {row['count']:>6} {row['pnl']:>12.6f}")
+            print(f"{'closed':<14} {ta['n_closed']:>6} "
+                  f"{ta['realized_pnl']:>12.6f}   open {ta['n_open']}, "
+                  f"kept {len(trades)} of {stats['n_records']} records")
+            path = eng.last_saved.with_name(
+                eng.last_saved.stem + "_trades.csv")
+            with open(path, "w", newline="") as f:
+                w = csv.DictWriter(f, fieldnames=[*FIELDS, "duration"])
+                w.writeheader()
+                w.writerows(trades)
+            print(f"trades -> {path}")
         return
 
     if args.cmd == "optimize":

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Per-kernel microbenchmarks (GPU): backtest (vote, grid, DCA), Monte-Carlo, covariance,
+"""Per-kernel microbenchmarks (GPU): backtest (vote, grid, DCA, ledger), Monte-Carlo, covariance,
 indicators, LSTM fwd/bwd, GA evolve, env step, GAE.
 
 Used for rocprofv3 runs and optimization A/Bs:
@@ -91,6 +91,44 @@ def bench_backtest_grid(reps):
 
 def bench_backtest_dca(reps):
     return _bench_family("dca", reps)
+
+
+def bench_ledger(reps):
+    """The inspection shape of backtest_ledger.hip: few strategies, many
+    symbols, a long history, one equity sample per day. The twin's time
+    for the same call is not run but SCALED: it is measured on one symbol
+    and 20k candles and multiplied by the candle ratio (the twin is a
+    per-candle numpy loop vectorized over lanes, so per-candle cost at
+    64x the lanes is at least this)."""
+    from ai_crypto_trader_amd.backtesting.engine_cpu import run_backtest_cpu
+    from ai_crypto_trader_amd.backtesting.strategy import random_population
+    from ai_crypto_trader_amd.data.synthetic import (
+        candles_chl_v, generate_ohlcv,
+    )
+    from ai_crypto_trader_amd.ops.backtest import run_backtest_ledger_gpu
+
+    nsym, T, P, stride, cap = 64, 1_000_000, 8, 1440, 4096
+    market = candles_chl_v(generate_ohlcv(T, nsym, seed=0))
+    candles = torch.from_numpy(market).cuda()
+    pop_np = random_population(P, seed=1)
+    pop = torch.from_numpy(pop_np).cuda()
+    kw = dict(max_trades=cap, equity_stride=stride)
+    dt = timed(lambda: run_backtest_ledger_gpu(candles, pop, **kw), reps)
+    led = run_backtest_ledger_gpu(candles, pop, **kw)
+    torch.cuda.synchronize()
+    T_cpu = 20_000
+    t0 = time.perf_counter()
+    run_backtest_cpu(market[:1, :T_cpu], pop_np, record_trades=True, **kw)
+    cpu_per_candle = (time.perf_counter() - t0) / T_cpu
+    return {"kernel": "ledger", "ms": dt * 1e3,
+            "candles_per_sec": P * nsym * T / dt,
+            "records_per_lane": float(led.n_records.float().mean()),
+            "records_max": int(led.n_records.max()),
+            "twin_ms_per_candle_1sym": cpu_per_candle * 1e3,
+            "twin_s_scaled_to_T": cpu_per_candle * T,
+            "config": {"nsym": nsym, "T": T, "P": P,
+                       "equity_stride": stride, "max_trades": cap,
+                       "twin_measured_on": {"nsym": 1, "T": T_cpu}}}
 
 
 def bench_mc(reps):
@@ -259,7 +297,7 @@ def bench_gae(reps):
 
 BENCHES = {
     "backtest": bench_backtest, "backtest_grid": bench_backtest_grid,
-    "backtest_dca": bench_backtest_dca, "mc": bench_mc, "mc_bootstrap": bench_mc_bootstrap, "cov": bench_cov,
+    "backtest_dca": bench_backtest_dca, "ledger": bench_ledger, "mc": bench_mc, "mc_bootstrap": bench_mc_bootstrap, "cov": bench_cov,
     "indicators": bench_indicators, "lstm": bench_lstm, "gru": bench_gru, "env": bench_env,
     "gae": bench_gae, "attn": bench_attn,
 }
