@@ -44,6 +44,9 @@ __global__ void __launch_bounds__(256) cov_accum_kernel(
     const int my_col = threadIdx.x % N;
     const int my_row0 = threadIdx.x / N;        // 256/N rows per pass
     const int rows_per_pass = 256 / N;
+    // N = 48 tiles only 240 of the 256 threads: the rest would re-add
+    // rows my_row0, my_row0 + rows_per_pass, ... of columns 0..15
+    const bool sums_col = my_row0 < rows_per_pass;
 
     if (threadIdx.x < 64) lds_sx[threadIdx.x] = 0.0f;
 
@@ -85,8 +88,10 @@ __global__ void __launch_bounds__(256) cov_accum_kernel(
             }
         }
         // column sums (for the mean term)
-        for (int r = my_row0; r < nrow; r += rows_per_pass)
-            colsum += tile[r * COV_PAD + my_col];
+        if (sums_col) {
+            for (int r = my_row0; r < nrow; r += rows_per_pass)
+                colsum += tile[r * COV_PAD + my_col];
+        }
     }
 
     __syncthreads();

@@ -35,7 +35,8 @@ def lagged_corr_gpu(a, b, max_lag: int):
     import torch
 
     ops = require_hip_ops()
-    assert a.is_cuda and b.is_cuda and a.dtype == torch.float32
+    assert a.is_cuda and b.is_cuda
+    assert a.dtype == torch.float32 and b.dtype == torch.float32
     n = int(min(a.numel(), b.numel()))
     a = a[:n].contiguous()
     b = b[:n].contiguous()
