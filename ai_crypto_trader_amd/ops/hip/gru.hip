@@ -12,6 +12,8 @@
 // the h-side differs only in the n column (da_n * r), applied on the
 // torch side for the dW_hh GEMM (models/gru.py).
 
+#include <stdexcept>
+
 #include "common.hpp"
 
 typedef __bf16 bf16;
@@ -242,7 +244,7 @@ extern "C" void launch_gru_seq_fwd(const void* xproj, const void* Wt,
                                    void* gates_out, float* hpn_out, int B,
                                    int T, int H, int save_mode,
                                    hipStream_t stream) {
-    if (B % GRU_BM != 0)
+    if (B <= 0 || B % GRU_BM != 0)
         throw std::runtime_error("gru_fwd: B must be a multiple of 64");
     dim3 grid(B / GRU_BM);
     if (H == 64) {
@@ -264,7 +266,7 @@ extern "C" void launch_gru_seq_bwd(const float* dh_up, const void* gates,
                                    const float* hpn_sav, const void* h_out,
                                    const void* W, void* dgates_out, int B,
                                    int T, int H, hipStream_t stream) {
-    if (B % GRU_BM != 0)
+    if (B <= 0 || B % GRU_BM != 0)
         throw std::runtime_error("gru_bwd: B must be a multiple of 64");
     dim3 grid(B / GRU_BM);
     if (H == 64) {

@@ -9,8 +9,9 @@ which hold the HIP kernels to the same envelopes. No constant here was
 fitted to a GPU result: each is derived below from the number formats and
 the kernel's launch geometry, with its margin fixed by the CPU emulation.
 
-Units: U24 = 2^-24 is the f32 unit roundoff, B8 = 2^-8 one bf16 ulp
-(relative); a round-to-nearest bf16 store is off by at most B8/2.
+Units: U24 = 2^-24 is the f32 unit roundoff and B8 = 2^-8 the bf16 one
+(8 significant bits); a round-to-nearest bf16 store of x is off by up to
+B8 |x|, reached just above a power of two.
 """
 
 import numpy as np

@@ -213,6 +213,14 @@ def test_mfma_bf16_layout(dev):
     torch.testing.assert_close(C.cpu(), ref, rtol=2e-2, atol=2e-2)
 
 
+def _randomize_biases(layer):
+    """The layers initialise b_ih and b_hh to zero; a test that leaves
+    them there cannot see how the kernels index or place them."""
+    with torch.no_grad():
+        layer.b_ih.uniform_(-0.5, 0.5)
+        layer.b_hh.uniform_(-0.5, 0.5)
+
+
 @pytest.mark.parametrize("H", [64, 32])
 def test_lstm_fwd_matches_reference(dev, H):
     from ai_crypto_trader_amd.models.lstm import FusedLSTMLayer
@@ -220,6 +228,7 @@ def test_lstm_fwd_matches_reference(dev, H):
     torch.manual_seed(0)
     T, B, F = 20, 128, 9
     layer = FusedLSTMLayer(F, H)
+    _randomize_biases(layer)
     x = torch.randn(T, B, F)
     ref = layer._forward_reference(x)           # fp32 CPU reference
     layer_g = layer.to(dev)
@@ -231,12 +240,15 @@ def test_lstm_fwd_matches_reference(dev, H):
     )
 
 
-def test_lstm_bwd_matches_reference(dev):
+@pytest.mark.parametrize("B", [64, 128, 40])      # 40: the pad-to-64 path
+@pytest.mark.parametrize("H", [64, 32])
+def test_lstm_bwd_matches_reference(dev, H, B):
     from ai_crypto_trader_amd.models.lstm import FusedLSTMLayer
 
     torch.manual_seed(1)
-    T, B, F, H = 12, 64, 9, 64
+    T, F = 12, 9
     layer_ref = FusedLSTMLayer(F, H)
+    _randomize_biases(layer_ref)
     layer_gpu = FusedLSTMLayer(F, H)
     layer_gpu.load_state_dict(layer_ref.state_dict())
     layer_gpu = layer_gpu.to(dev)
@@ -259,6 +271,8 @@ def test_lstm_bwd_matches_reference(dev):
     assert rel(layer_gpu.w_hh.grad.cpu().float(), layer_ref.w_hh.grad) < 0.08
     assert rel(layer_gpu.w_ih.grad.cpu().float(), layer_ref.w_ih.grad) < 0.08
     assert rel(layer_gpu.b_hh.grad.cpu().float(), layer_ref.b_hh.grad) < 0.08
+    assert rel(layer_gpu.b_ih.grad.cpu().float(), layer_ref.b_ih.grad) < 0.08
+    assert out_g.shape == (T, B, H) and xg.grad.shape == (T, B, F)
 
 
 def test_lstm_predictor_trains(dev):
@@ -350,6 +364,7 @@ def test_gru_fwd_matches_reference(dev, H):
     torch.manual_seed(4)
     T, B, F = 20, 128, 9
     layer = FusedGRULayer(F, H)
+    _randomize_biases(layer)
     x = torch.randn(T, B, F)
     ref = layer._forward_reference(x)
     out = layer.to(dev)(x.to(dev))
@@ -358,12 +373,15 @@ def test_gru_fwd_matches_reference(dev, H):
                                atol=5e-2)
 
 
-def test_gru_bwd_matches_reference(dev):
+@pytest.mark.parametrize("B", [64, 128, 40])      # 40: the pad-to-64 path
+@pytest.mark.parametrize("H", [64, 32])
+def test_gru_bwd_matches_reference(dev, H, B):
     from ai_crypto_trader_amd.models.gru import FusedGRULayer
 
     torch.manual_seed(5)
-    T, B, F, H = 12, 64, 9, 64
+    T, F = 12, 9
     ref_l = FusedGRULayer(F, H)
+    _randomize_biases(ref_l)
     gpu_l = FusedGRULayer(F, H)
     gpu_l.load_state_dict(ref_l.state_dict())
     gpu_l = gpu_l.to(dev)
@@ -381,6 +399,9 @@ def test_gru_bwd_matches_reference(dev):
     assert rel(xg.grad.cpu().float(), x.grad) < 0.08
     assert rel(gpu_l.w_hh.grad.cpu().float(), ref_l.w_hh.grad) < 0.08
     assert rel(gpu_l.w_ih.grad.cpu().float(), ref_l.w_ih.grad) < 0.08
+    assert rel(gpu_l.b_ih.grad.cpu().float(), ref_l.b_ih.grad) < 0.08
+    assert rel(gpu_l.b_hh.grad.cpu().float(), ref_l.b_hh.grad) < 0.08
+    assert xg.grad.shape == (T, B, F)
 
 
 def test_model_zoo_trains_on_gpu(dev):
@@ -722,18 +743,42 @@ def test_mc_bootstrap_matches_cpu(dev):
     assert abs(float(fv.mean()) - expect) < 0.05
 
 
-def test_gru_infer_matches_training_forward(dev):
+@pytest.mark.parametrize("H", [64, 32])
+def test_gru_infer_matches_training_forward(dev, H):
     """The no-save GRU inference forward produces the same hidden states
     as the training forward (mirrors the LSTM serving path)."""
     from ai_crypto_trader_amd.models.gru import FusedGRULayer
 
     torch.manual_seed(3)
-    layer = FusedGRULayer(9, 64).to(dev)
+    layer = FusedGRULayer(9, H)
+    _randomize_biases(layer)
+    layer = layer.to(dev)
     x = torch.randn(24, 128, 9, device=dev)
     with torch.enable_grad():
         h_train = layer(x)
     with torch.no_grad():
         h_infer = layer(x)
     torch.cuda.synchronize()
+    np.testing.assert_array_equal(h_train.detach().cpu().float().numpy(),
+                                  h_infer.cpu().float().numpy())
+
+
+@pytest.mark.parametrize("H", [64, 32])
+def test_lstm_infer_matches_training_forward(dev, H):
+    """The no-save LSTM inference forward (the serving path) produces the
+    same hidden states as the training forward."""
+    from ai_crypto_trader_amd.models.lstm import FusedLSTMLayer
+
+    torch.manual_seed(3)
+    layer = FusedLSTMLayer(9, H)
+    _randomize_biases(layer)
+    layer = layer.to(dev)
+    x = torch.randn(24, 128, 9, device=dev)
+    with torch.enable_grad():
+        h_train = layer(x)
+    with torch.no_grad():
+        h_infer = layer(x)
+    torch.cuda.synchronize()
+    assert h_train.requires_grad and not h_infer.requires_grad
     np.testing.assert_array_equal(h_train.detach().cpu().float().numpy(),
                                   h_infer.cpu().float().numpy())
