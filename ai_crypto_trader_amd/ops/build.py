@@ -34,6 +34,7 @@ SOURCES = [
     "laggedcorr.hip",
     "histogram.hip",
     "rl_env.hip",
+    "rng_probe.hip",
     "bindings.cpp",
 ]
 

@@ -72,6 +72,11 @@ extern "C" void launch_mfma_gemm_test(const void*, const void*, float*, int,
                                       int, int, hipStream_t);
 extern "C" void launch_mfma_gemm_test_bf16(const void*, const void*, float*,
                                            int, int, int, hipStream_t);
+extern "C" void launch_philox_probe(const uint64_t*, const uint64_t*,
+                                    uint32_t*, float*, uint64_t, long,
+                                    hipStream_t);
+extern "C" void launch_box_muller_probe(const uint32_t*, const uint32_t*,
+                                        float*, long, hipStream_t);
 extern "C" void launch_gru_seq_fwd(const void*, const void*, const float*,
                                    void*, void*, float*, int, int, int,
                                    int, hipStream_t);
@@ -341,6 +346,31 @@ PYBIND11_MODULE(_hip_ops, m) {
                                          reinterpret_cast<float*>(c), M, N,
                                          K, as_stream(stream));
               check(hipGetLastError(), "mfma_gemm_test_bf16 launch");
+          });
+
+    // test-only: the device RNG of common.hpp, seen directly
+    // (ctr_lo/ctr_hi (n,) u64 -> words (n,4) u32, normals (n,4) f32)
+    m.def("philox_probe",
+          [](uint64_t seed, uintptr_t ctr_lo, uintptr_t ctr_hi,
+             uintptr_t words, uintptr_t normals, long n, uintptr_t stream) {
+              launch_philox_probe(reinterpret_cast<const uint64_t*>(ctr_lo),
+                                  reinterpret_cast<const uint64_t*>(ctr_hi),
+                                  reinterpret_cast<uint32_t*>(words),
+                                  reinterpret_cast<float*>(normals), seed, n,
+                                  as_stream(stream));
+              check(hipGetLastError(), "philox_probe launch");
+          });
+
+    // test-only: box_muller on chosen uniform words (a, b (n,) u32 ->
+    // out (n,2) f32)
+    m.def("box_muller_probe",
+          [](uintptr_t a, uintptr_t b, uintptr_t out, long n,
+             uintptr_t stream) {
+              launch_box_muller_probe(reinterpret_cast<const uint32_t*>(a),
+                                      reinterpret_cast<const uint32_t*>(b),
+                                      reinterpret_cast<float*>(out), n,
+                                      as_stream(stream));
+              check(hipGetLastError(), "box_muller_probe launch");
           });
 
     m.def("lstm_seq_fwd",

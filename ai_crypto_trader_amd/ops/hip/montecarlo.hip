@@ -267,6 +267,24 @@ __global__ void __launch_bounds__(512) mc_paths_mfma_kernel(
 
 }  // namespace
 
+// Launch parameters are rejected before any launch: t_hist = 0 would reach
+// a device modulo by zero, an unsupported A no kernel at all.
+static void mc_check_assets(const char* who, int n_assets) {
+    if (n_assets != 4 && n_assets != 8 && n_assets != 16 && n_assets != 32 &&
+        n_assets != 64)
+        throw std::runtime_error(
+            std::string(who) + ": n_assets must be one of 4/8/16/32/64");
+}
+
+static void mc_check_counts(const char* who, int n_steps, long n_paths) {
+    if (n_paths <= 0)
+        throw std::runtime_error(std::string(who) +
+                                 ": n_paths must be positive");
+    if (n_steps < 0)
+        throw std::runtime_error(std::string(who) +
+                                 ": n_steps must not be negative");
+}
+
 extern "C" void launch_mc_paths_mfma(const float* cvol, const float* drift,
                                      const float* wS0, float* final_value,
                                      float* max_dd, int n_assets,
@@ -275,10 +293,12 @@ extern "C" void launch_mc_paths_mfma(const float* cvol, const float* drift,
                                      int antithetic, hipStream_t stream) {
     if (n_assets != MCM_A)
         throw std::runtime_error("mc_paths_mfma: n_assets must be 64");
-    if (n_paths % MCM_PB != 0)
-        throw std::runtime_error(
-            "mc_paths_mfma: n_paths must be a multiple of 256");
-    long blocks = n_paths / MCM_PB;
+    mc_check_counts("mc_paths_mfma", n_steps, n_paths);
+    // any n_paths: the last block is ragged (the kernel guards its stores
+    // with p < n_paths), and half = n_paths / 2 is the caller's true count
+    long blocks = (n_paths + MCM_PB - 1) / MCM_PB;
+    if (blocks > 0x7fffffffL)
+        throw std::runtime_error("mc_paths_mfma: n_paths too large");
     hipLaunchKernelGGL(mc_paths_mfma_kernel, dim3((unsigned)blocks),
                        dim3(512), 0, stream, cvol, drift, wS0, final_value,
                        max_dd, n_steps, n_paths, v0, seed, path_base,
@@ -292,6 +312,8 @@ extern "C" void launch_mc_paths(const float* cvol, const float* drift,
                                 float v0, uint64_t seed, long path_base,
                                 int antithetic, hipStream_t stream) {
     (void)weights_unused;
+    mc_check_assets("mc_paths", n_assets);
+    mc_check_counts("mc_paths", n_steps, n_paths);
     long want = (n_paths + 255) / 256;
     int blocks = (int)(want < 8192 ? want : 8192);
     dim3 grid(blocks), block(256);
@@ -385,6 +407,10 @@ extern "C" void launch_mc_bootstrap(const float* logret, const float* wS0,
                                     int n_assets, int t_hist, int n_steps,
                                     long n_paths, float v0, uint64_t seed,
                                     long path_base, hipStream_t stream) {
+    mc_check_assets("mc_bootstrap", n_assets);
+    mc_check_counts("mc_bootstrap", n_steps, n_paths);
+    if (t_hist <= 0)
+        throw std::runtime_error("mc_bootstrap: t_hist must be positive");
     long want = (n_paths + 255) / 256;
     int blocks = (int)(want < 8192 ? want : 8192);
     dim3 grid(blocks), block(256);

@@ -151,13 +151,16 @@ def mc_paths_gpu(
 ):
     """GPU path generation; returns (final_value, max_dd) torch tensors.
 
-    use_mfma=None (auto): the bf16 MFMA pathgen kernel when A==64 and
-    n_paths is a multiple of 256, else the exact f32 VALU kernel. The two
-    draw identical Philox normals; MFMA quantizes Z/CVOL to bf16
-    (statistics agree to ~1e-2, see tests).
+    use_mfma=None (auto): the bf16 MFMA pathgen kernel when A==64 (any
+    n_paths; the last 256-path block may be ragged), else the exact f32
+    VALU kernel. The two draw identical Philox normals; MFMA quantizes
+    Z/CVOL to bf16 (statistics agree to ~1e-2, see tests).
 
     antithetic=True pairs the top half of the path range with the bottom
-    half's normals negated (antithetic variates): an unbiased estimator
+    half's normals negated (antithetic variates): with half = n_paths // 2,
+    path p >= half takes the counter of path p - half, in both kernels (at
+    odd n_paths the last path negates counter `half`, which no unmirrored
+    path draws: it has no partner). An unbiased estimator
     with reduced variance for the monotone risk statistics, at half the
     RNG cost per effective path. Off for benchmarks (iid paths)."""
     import torch
@@ -168,7 +171,6 @@ def mc_paths_gpu(
         use_mfma = (A == 64)
     if use_mfma and A != 64:
         use_mfma = False
-    pad = ((-n_paths) % 256) if use_mfma else 0   # MFMA tile = 256 paths
     f32 = np.float32
     cvol_k_major, drift = _gbm_terms(chol, mu, sigma, dt)      # base-2 log
     wS0 = (np.asarray(weights) * s0).astype(f32)
@@ -177,17 +179,17 @@ def mc_paths_gpu(
     t_cvol = torch.from_numpy(cvol_k_major).to(device)
     t_drift = torch.from_numpy(drift).to(device)
     t_w = torch.from_numpy(wS0).to(device)
-    fv = torch.empty(n_paths + pad, dtype=torch.float32, device=device)
-    dd = torch.empty(n_paths + pad, dtype=torch.float32, device=device)
+    fv = torch.empty(n_paths, dtype=torch.float32, device=device)
+    dd = torch.empty(n_paths, dtype=torch.float32, device=device)
     stream = torch.cuda.current_stream(fv.device).cuda_stream
     if use_mfma:
+        # the true n_paths, never a padded one: the kernel derives the
+        # antithetic mirror boundary from it
         ops.mc_paths_mfma(
             t_cvol.data_ptr(), t_drift.data_ptr(), t_w.data_ptr(),
-            fv.data_ptr(), dd.data_ptr(), A, n_steps, n_paths + pad, v0,
+            fv.data_ptr(), dd.data_ptr(), A, n_steps, n_paths, v0,
             seed, path_base, int(antithetic), stream,
         )
-        if pad:
-            fv, dd = fv[:n_paths], dd[:n_paths]
     else:
         ops.mc_paths(
             t_cvol.data_ptr(), t_drift.data_ptr(), t_w.data_ptr(), 0,
