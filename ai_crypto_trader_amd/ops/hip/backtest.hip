@@ -22,7 +22,23 @@
 //     per window) march the f64 rolling sums into an LDS table
 //     [candle][window], then all 256 lanes convert its slots to
 //     {mean, std} in place, and every lane reads its window's slot
-//   - EMA/MACD/Wilder-RSI are O(1) register recurrences per candle
+//   - everything else a lane needs of a candle is one 32-byte LDS record,
+//     written by one thread per candle: {close, high, low, change} and
+//     the shared stochastic/Williams/trend vote inputs — two b128
+//     broadcasts off one address, and the close-to-close change is
+//     computed once per block, not once per lane
+//   - EMA/MACD/Wilder-RSI are O(1) register recurrences per candle; the
+//     EMAs are seeded with close[0], so no candle tests t == 0
+//   - the first WARMUP = 4 sub-tiles of a history run the recurrences
+//     only (no table conversion, no votes, no position machine), so the
+//     main lane loop carries no t >= WARMUP test
+//   - the lane loop is the whole cost (15625 candles x ~175 instructions
+//     a wave), so it holds no instruction the result does not need:
+//     bt_max / bt_min instead of canonicalising fmaxf / fminf, the
+//     trailing trigger computed at entry, thread-indexed LDS addresses
+//     rebuilt per tile instead of living through it. 31744 B of LDS and
+//     96 VGPR per lane keep five blocks on a CU; one dword of scratch is
+//     reloaded once per tile (see BtState::load)
 //   - the position state machine (SL/TP/trailing/vote exits — semantics of
 //     trade_executor_service.py:55-399 + binance_ml_strategy.py:489-543)
 //     matches backtesting/engine_cpu.py bit-for-bit (fp-contract off, same
@@ -51,27 +67,46 @@ struct BtState {
     {
         v.load(pr);
         pos.load(pr, initial_equity);
+        // Keep the two Williams thresholds in registers: left to itself
+        // the compiler recomputes stoch_* - 100 in every candle to save
+        // two VGPRs. Holding them costs one dword of scratch, reloaded
+        // once per tile, and measured 1.9% faster than the spill-free
+        // build (profiles/backtest_seg64_lane_loop.json).
+        asm volatile("" : "+v"(v.will_os), "+v"(v.will_ob));
     }
 
-    // `ms` = {mean, std} of this lane's Bollinger window at candle t
-    __device__ void step(int t, float close, float high, float low,
-                         float change, float2 ms, float4 sv)
+    // One candle at t >= WARMUP. `c` = {close, high, low, change} and `sv`
+    // = the shared votes, the candle's LDS record; `ms` = {mean, std} of
+    // this lane's Bollinger window at candle t. The EMAs were seeded.
+    __device__ void step(int t, float4 c, float2 ms, float4 sv)
     {
 #pragma clang fp contract(off)           // match the numpy f32 reference
         // --- 1+2. indicators, votes ----------------------------------
-        const int net =
-            v.count(t, close, v.recur(t, close, change), ms, sv);
+        const int net = v.count<false>(
+            t, c.x, v.recur<true>(t, c.x, c.w), ms, sv);
         // --- 3+4. position, mark to market; this kernel keeps only the
         // metrics, so what the candle did (the event) is dropped
-        pos.step(t, net, v.entry_v, v.exit_v, close, high, low);
+        pos.step<false>(t, net, v.entry_v, v.exit_v, c.x, c.y, c.z);
+    }
+
+    // One candle at t < WARMUP: no vote is taken, so nothing can be
+    // entered, the lane stays flat and its mark to market is the no-op
+    // BtPosition::step skips — only the recurrences advance.
+    __device__ void warm(int t, float4 c)
+    {
+        v.recur<true>(t, c.x, c.w);
     }
 };
 
 // Candles per fill of the Bollinger table. 32 candles x 32 window slots
-// x 16 B = 16 KB: with the staging, 27 KB per block, so the five blocks
-// per CU that the VGPR budget allows also fit its LDS.
+// x 16 B = 16 KB. With the staging (320 x (4 + 8 + 8) B = 6400 B), the
+// candle records (256 x 32 B = 8 KB) and the scan state (3 x 32 x 8 B)
+// that is 31744 B per block, so the five blocks per CU that the VGPR
+// budget allows also fit its 160 KB of LDS.
 #define BT_BBSUB 32
 static_assert(BT_TILE % BT_BBSUB == 0, "sub-tiles must tile the tile");
+static_assert(BT_WARMUP % BT_BBSUB == 0 && BT_WARMUP <= BT_TILE,
+              "the warm-up is whole sub-tiles of the first tile");
 static_assert(BT_BLOCK % BT_MAXWIN == 0 && BT_BBSUB <= BT_BLOCK &&
                   (BT_MAXWIN & (BT_MAXWIN - 1)) == 0,
               "a lane converts slots of one window only");
@@ -110,7 +145,9 @@ __global__ void __launch_bounds__(BT_BLOCK, 5) backtest_kernel(
     __shared__ float chist[BT_SPAN];     // close history incl. halo
     __shared__ double csq[BT_SPAN];      // (double)close^2, same span
     __shared__ float hl[BT_SPAN][2];     // high, low
-    __shared__ float4 sh_vote[BT_TILE];  // bt_shared_votes() per candle
+    // one record per candle: {close, high, low, change}, then the shared
+    // votes (bt_shared_votes<true>) — two b128 broadcasts off one address
+    __shared__ float4 rec[BT_TILE][2];
     // Bollinger table [sub-tile candle][window - 2]; slot 31 is padding
     __shared__ float4 bbtab[BT_BBSUB * BT_MAXWIN];
     // per window slot: the rolling sums between sub-tiles, and 1/w
@@ -131,11 +168,9 @@ __global__ void __launch_bounds__(BT_BLOCK, 5) backtest_kernel(
     // strategies the block holds, active or not. Its sums live in LDS
     // between sub-tiles, so no lane carries f64 state through the candle
     // loop.
-    const int scan_w = tid + 2;
-    const bool is_scan = scan_w <= BT_MAXWIN;
     if (tid < BT_MAXWIN) {
         BollState b;
-        b.init(scan_w);
+        b.init(tid + 2);
         sh_sum[tid] = b.sum;
         sh_sum2[tid] = b.sum2;
         sh_invw[tid] = b.inv_w;
@@ -144,12 +179,25 @@ __global__ void __launch_bounds__(BT_BLOCK, 5) backtest_kernel(
         bbtab[tid * BT_MAXWIN + BT_MAXWIN - 1] =
             make_float4(0.0f, 0.0f, 0.0f, 0.0f);
 
-    float prev_close = 0.f;
     const float4* sym_candles =
         reinterpret_cast<const float4*>(candles + (long)sym * T * 4);
+    // Seed the EMAs with this symbol's first close instead of selecting on
+    // t == 0 in every candle: candle 0 then computes x + a * (x - x), which
+    // is x exactly for any finite a, and the alphas 2 / (period + 1) of
+    // parameters within PARAM_BOUNDS lie in (0, 1].
+    if (T > 0) st.v.ema_f = st.v.ema_s = sym_candles[0].x;
 
     for (int t0 = 0; t0 < T; t0 += BT_TILE) {
-        bt_stage_tile(sym_candles, t0, T, chist, hl, csq);
+        // A copy of tid the compiler cannot see through. The staging, the
+        // scan and the conversion address LDS by thread; derived from tid
+        // itself, a dozen such addresses were hoisted to kernel entry and
+        // then spilled around the lane loop. From this copy they are
+        // recomputed once per tile.
+        int ltid = tid;
+        asm volatile("" : "+v"(ltid));
+        const int scan_w = ltid + 2;
+        const bool is_scan = scan_w <= BT_MAXWIN;
+        bt_stage_tile(sym_candles, t0, T, chist, hl, csq, ltid);
         const int tend = min(BT_TILE, T - t0);
         // BB resnap at RESNAP-aligned tiles (engine_cpu.py lockstep):
         // window closes for candle t0 are chist[BT_HALO - j], j < w; the
@@ -159,12 +207,14 @@ __global__ void __launch_bounds__(BT_BLOCK, 5) backtest_kernel(
         if (resnap_tile && is_scan) {
             BollState b;
             b.resnap(scan_w, &chist[BT_HALO]);
-            sh_sum[tid] = b.sum;
-            sh_sum2[tid] = b.sum2;
+            sh_sum[ltid] = b.sum;
+            sh_sum2[ltid] = b.sum2;
         }
-        bt_shared_votes(t0, tend, chist, hl, sh_vote);
+        bt_shared_votes<true>(t0, tend, chist, hl, &rec[0][0], ltid);
         for (int s0 = 0; s0 < tend; s0 += BT_BBSUB) {
             const int send = min(s0 + BT_BBSUB, tend);
+            // a warm-up sub-tile lies below WARMUP as a whole
+            const bool warm = t0 + s0 < BT_WARMUP;
             // the previous sub-tile's readers are done with the table
             // (s0 == 0: bt_stage_tile's barriers already say so)
             if (s0 > 0) __syncthreads();
@@ -173,28 +223,35 @@ __global__ void __launch_bounds__(BT_BLOCK, 5) backtest_kernel(
             // but nothing else does; a slot gets the sums as of its candle
             if (is_scan) {
                 BollState b;
-                b.sum = sh_sum[tid];
-                b.sum2 = sh_sum2[tid];
+                b.sum = sh_sum[ltid];
+                b.sum2 = sh_sum2[ltid];
 #pragma unroll 4
                 for (int tt = s0; tt < send; ++tt) {
                     const int i = tt + BT_HALO;
                     if (!(resnap_tile && tt == 0))
                         b.advance(chist[i], chist[i - scan_w], csq[i],
                                   csq[i - scan_w]);
-                    bbtab[(tt - s0) * BT_MAXWIN + tid] =
+                    bbtab[(tt - s0) * BT_MAXWIN + ltid] =
                         bt_pack_sums(b.sum, b.sum2);
                 }
-                sh_sum[tid] = b.sum;
-                sh_sum2[tid] = b.sum2;
+                sh_sum[ltid] = b.sum;
+                sh_sum2[ltid] = b.sum2;
             }
-            __syncthreads();
+            __syncthreads();             // sums (and the records) visible
+            if (warm) {
+                // no vote reads the table before WARMUP: the recurrences
+                // advance, phase B and the position machine are skipped
+                for (int tt = s0; tt < send; ++tt)
+                    st.warm(t0 + tt, rec[tt][0]);
+                continue;
+            }
             // phase B, the whole block: sums -> {mean, std} in place, the
             // f64 multiplies and the sqrt spread over all lanes. A lane's
             // slots all belong to one window (BT_BLOCK % BT_MAXWIN == 0).
             {
                 BollState b;
-                b.inv_w = sh_invw[tid & (BT_MAXWIN - 1)];
-                for (int e = tid; e < (send - s0) * BT_MAXWIN;
+                b.inv_w = sh_invw[ltid & (BT_MAXWIN - 1)];
+                for (int e = ltid; e < (send - s0) * BT_MAXWIN;
                      e += BT_BLOCK) {
                     const float4 v = bbtab[e];
                     b.sum = bt_unpack_sum(v.x, v.y);
@@ -204,26 +261,25 @@ __global__ void __launch_bounds__(BT_BLOCK, 5) backtest_kernel(
                     bbtab[e].y = ms.y;
                 }
             }
-            __syncthreads();             // table (and sh_vote) visible
+            __syncthreads();             // table visible
             for (int tt = s0; tt < send; ++tt) {
-                const int t = t0 + tt;
-                const float close = chist[tt + BT_HALO];
-                const float high = hl[tt + BT_HALO][0];
-                const float low = hl[tt + BT_HALO][1];
-                const float change = (t == 0) ? 0.0f : close - prev_close;
-                const float4 sv = sh_vote[tt];   // b128 broadcast
                 // b64 per lane: equal windows broadcast, distinct windows
                 // sit 16 B apart (w and w + 16 share banks: 2-way at most)
                 const float4* e = &my_bb[(tt - s0) * BT_MAXWIN];
-                st.step(t, close, high, low, change,
-                        make_float2(e->x, e->y), sv);
-                prev_close = close;
+                st.step(t0 + tt, rec[tt][0], make_float2(e->x, e->y),
+                        rec[tt][1]);
             }
         }
     }
 
-    if (act)
-        st.pos.acc.finalize(metrics + ((long)p * nsym + sym) * BT_NMETRIC, T);
+    // p again from an opaque tid, as above: otherwise it is spilled at
+    // entry and reloaded here
+    int otid = tid;
+    asm volatile("" : "+v"(otid));
+    const int po = chunk * BT_BLOCK + otid;
+    if (po < P)
+        st.pos.acc.finalize(metrics + ((long)po * nsym + sym) * BT_NMETRIC,
+                            T);
 }
 
 }  // namespace

@@ -17,6 +17,57 @@
 // rounds to the neighbor 0x44353ee5 and biases every sharpe by 1 ulp
 #define BT_ANNUALIZE 0x1.6a7dccp+9f
 
+// max / min as ONE instruction. fmaxf / fminf on a loop-carried or loaded
+// value compile to a self-max canonicalisation (v_max_f32 x, x, x, which
+// quiets a signalling NaN) plus the max itself; per candle and lane that
+// was 7 extra VALU in backtest_kernel. The bare instruction returns the
+// same bits as fmaxf / fminf for every operand pair that holds no
+// SIGNALLING NaN — including a quiet NaN against a number, where both give
+// the number. Arithmetic results are never signalling NaNs, and candle
+// inputs are assumed finite, so the call sites below (running maxima and
+// minima of prices, equities and averages) qualify. Where the compiler
+// already emits one instruction (fmaxf(change, 0.0f) and the like, with a
+// folded negate) keep fmaxf.
+__device__ __forceinline__ float bt_max(float a, float b)
+{
+    float r;
+    asm("v_max_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
+    return r;
+}
+
+__device__ __forceinline__ float bt_min(float a, float b)
+{
+    float r;
+    asm("v_min_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
+    return r;
+}
+
+// bt_max against a wave-uniform value (a constant): it sits in a scalar
+// register, so the loop holds no VGPR for it
+__device__ __forceinline__ float bt_max_uniform(float uniform, float b)
+{
+    float r;
+    asm("v_max_f32 %0, %1, %2" : "=v"(r) : "s"(uniform), "v"(b));
+    return r;
+}
+
+// max(x, 0) and max(-x, 0), the negate folded into the instruction: what
+// fmaxf(x, 0.0f) and fmaxf(-x, 0.0f) compile to when x is an arithmetic
+// result, and also when x was loaded (where fmaxf canonicalises first)
+__device__ __forceinline__ float bt_pos_part(float x)
+{
+    float r;
+    asm("v_max_f32 %0, 0, %1" : "=v"(r) : "v"(x));
+    return r;
+}
+
+__device__ __forceinline__ float bt_neg_part(float x)
+{
+    float r;
+    asm("v_max_f32 %0, -%1, 0" : "=v"(r) : "v"(x));
+    return r;
+}
+
 // The ten metrics from scalars (engine_cpu.finalize_metrics semantics).
 // A free function because bt_trades_kernel holds the inputs in two
 // different waves' registers, not in one BtAccum.
@@ -69,8 +120,8 @@ struct BtAccum {
         sum_ret += r;
         sum_ret2 += r * r;
         equity = new_eq;
-        max_eq = fmaxf(max_eq, equity);
-        max_dd = fmaxf(max_dd, (max_eq - equity) / max_eq);
+        max_eq = bt_max(max_eq, equity);
+        max_dd = bt_max(max_dd, (max_eq - equity) / max_eq);
     }
 
     __device__ void finalize(float* __restrict__ out, int T) const

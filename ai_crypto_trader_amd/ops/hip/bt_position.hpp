@@ -27,26 +27,33 @@ struct BtEvent {
 
 // position + metrics state of one strategy
 struct BtPosition {
-    float size_pct, sl_pct, tp_pct, trail_pct, trail_act;
+    float size_pct, sl_pct, tp_pct;
+    float trail_m, act_m;     // 1 - trailing_stop_pct, 1 + trailing_act_pct
+    bool trail_en;            // trailing_stop_pct > 0
     float cash, units;
     bool in_pos;
     float entry_cost, entry_price;
+    float trail_trig;         // entry_price * act_m: constant while in
     float stop, tp, peak;
     BtAccum acc;
 
     __device__ void load(const float* __restrict__ pr, float initial_equity)
     {
+#pragma clang fp contract(off)
         size_pct = pr[12]; sl_pct = pr[13]; tp_pct = pr[14];
-        trail_pct = pr[15]; trail_act = pr[16];
+        trail_m = 1.0f - pr[15]; act_m = 1.0f + pr[16];
+        trail_en = pr[15] > 0.0f;
         cash = initial_equity; units = 0.f;
         in_pos = false;
-        entry_cost = entry_price = stop = tp = peak = 0.f;
+        entry_cost = entry_price = trail_trig = stop = tp = peak = 0.f;
         acc.init(initial_equity);
     }
 
     // One candle: `net` is the vote count, entry_v / exit_v the
     // strategy's thresholds. A caller that ignores the returned event
-    // pays nothing for it.
+    // pays nothing for it. WARM_TEST = false is for a caller that only
+    // comes here with t >= WARMUP.
+    template <bool WARM_TEST = true>
     __device__ BtEvent step(int t, int net, int entry_v, int exit_v,
                             float close, float high, float low)
     {
@@ -54,11 +61,10 @@ struct BtPosition {
         BtEvent ev = {BT_EV_NONE, 0.0f, 0.0f};
         // --- 3. position management ----------------------------------
         if (in_pos) {
-            peak = fmaxf(peak, high);
-            bool trail_on = (trail_pct > 0.0f) &&
-                            (peak >= entry_price * (1.0f + trail_act));
+            peak = bt_max(peak, high);
+            bool trail_on = trail_en && (peak >= trail_trig);
             if (trail_on)
-                stop = fmaxf(stop, peak * (1.0f - trail_pct));
+                stop = bt_max(stop, peak * trail_m);
             bool hit_sl = low <= stop;
             bool hit_tp = !hit_sl && high >= tp;
             bool hit_sig = !hit_sl && !hit_tp && net <= -exit_v;
@@ -74,12 +80,13 @@ struct BtPosition {
                 units = 0.0f;
                 in_pos = false;
             }
-        } else if (t >= BT_WARMUP && net >= entry_v) {
-            float cost = fminf(size_pct * acc.equity, cash);
+        } else if ((!WARM_TEST || t >= BT_WARMUP) && net >= entry_v) {
+            float cost = bt_min(size_pct * acc.equity, cash);
             units = cost * (1.0f - BT_FEE) / close;
             cash -= cost;
             entry_cost = cost;
             entry_price = close;
+            trail_trig = close * act_m;
             stop = close * (1.0f - sl_pct);
             tp = close * (1.0f + tp_pct);
             peak = close;

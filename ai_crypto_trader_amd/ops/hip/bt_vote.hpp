@@ -143,10 +143,14 @@ struct VoteState {
     // Wilder RSI, as the numerators/denominators the votes compare.
     struct Osc { float macd_hist, rsi_num, rsi_den; };
 
+    // SEEDED: the caller set ema_f = ema_s = close[0] before candle 0, so
+    // candle 0 needs no select (backtest_kernel, where the seed is set,
+    // says why that gives the same bits), and reads `change` from LDS
+    template <bool SEEDED = false>
     __device__ Osc recur(int t, float close, float change)
     {
 #pragma clang fp contract(off)           // match the numpy f32 reference
-        if (t == 0) { ema_f = close; ema_s = close; }
+        if (!SEEDED && t == 0) { ema_f = close; ema_s = close; }
         else {
             ema_f += a_f * (close - ema_f);
             ema_s += a_s * (close - ema_s);
@@ -156,20 +160,27 @@ struct VoteState {
         Osc o;
         o.macd_hist = macd - sig;
 
-        float gain = fmaxf(change, 0.0f);
-        float loss = fmaxf(-change, 0.0f);
+        // one instruction each for a `change` the caller computed; the
+        // seeded caller loads it, which fmaxf would canonicalise first
+        float gain = SEEDED ? bt_pos_part(change) : fmaxf(change, 0.0f);
+        float loss = SEEDED ? bt_neg_part(change) : fmaxf(-change, 0.0f);
         avg_gain += (gain - avg_gain) * inv_rsi_p;
         avg_loss += (loss - avg_loss) * inv_rsi_p;
         // division-free RSI votes (engine_cpu.py): rsi<thr <=>
         // 100*ag < thr*(ag+al')
         o.rsi_num = 100.0f * avg_gain;
-        o.rsi_den = avg_gain + fmaxf(avg_loss, BT_EPS);
+        // (bt_flags_kernel keeps fmaxf: with bt_max its continuous path
+        // measured 0.16% slower, profiles/backtest_seg64_lane_loop.json)
+        o.rsi_den = avg_gain + (SEEDED ? bt_max_uniform(BT_EPS, avg_loss)
+                                       : fmaxf(avg_loss, BT_EPS));
         return o;
     }
 
     // Part 3, the 6-indicator TradingSignal vote count: net = buys -
     // sells (0 before WARMUP). `ms` is BollState::stats() of this
-    // strategy's window at candle t.
+    // strategy's window at candle t. WARM_TEST = false is for a caller
+    // that only comes here with t >= WARMUP.
+    template <bool WARM_TEST = true>
     __device__ int count(int t, float close, Osc o, float2 ms,
                          float4 sv) const
     {
@@ -180,7 +191,7 @@ struct VoteState {
         float bb_den = fmaxf(2.0f * band, BT_EPS);
 
         int net = 0;
-        if (t >= BT_WARMUP) {
+        if (!WARM_TEST || t >= BT_WARMUP) {
             int buy = (o.rsi_num < rsi_os * o.rsi_den) +
                       (o.macd_hist > 0.0f) +
                       (bb_num < bb_bth * bb_den) +
@@ -218,15 +229,16 @@ struct VoteState {
 // Stage candles [t0 - HALO, t0 + TILE) of one symbol into LDS, zero-filled
 // outside [0, T): closes into chist, (high, low) into hl and, when csq is
 // given, (double)close^2 into csq. Barriers on both sides: the previous
-// tile's readers are done before, the tile is visible after.
+// tile's readers are done before, the tile is visible after. `tid` is
+// the thread's index in the block, for a caller that has its own copy.
 __device__ inline void bt_stage_tile(
     const float4* __restrict__ sym_candles, int t0, int T,
     float* __restrict__ chist, float (*__restrict__ hl)[2],
-    double* __restrict__ csq)
+    double* __restrict__ csq, int tid = threadIdx.x)
 {
 #pragma clang fp contract(off)
     __syncthreads();
-    for (int i = threadIdx.x; i < BT_SPAN; i += BT_BLOCK) {
+    for (int i = tid; i < BT_SPAN; i += BT_BLOCK) {
         const int t = t0 - BT_HALO + i;
         float4 c = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
         if (t >= 0 && t < T) c = sym_candles[t];
@@ -247,12 +259,18 @@ __device__ inline void bt_stage_tile(
 // lane loop needs one b128 broadcast read per candle. Finite windows over
 // the staged halo: exact wherever the tile starts. The caller's barrier
 // publishes sh_vote.
+//
+// RECORD = true writes one 32-byte record per candle instead, sh_vote
+// being [BT_TILE][2]: {close, high, low, change} then the votes, so a lane
+// loop reads a whole candle from one address. change = close[t] -
+// close[t - 1], 0 at t = 0; the halo holds the previous tile's last close.
+template <bool RECORD = false>
 __device__ inline void bt_shared_votes(
     int t0, int tend, const float* __restrict__ chist,
-    const float (*__restrict__ hl)[2], float4* __restrict__ sh_vote)
+    const float (*__restrict__ hl)[2], float4* __restrict__ sh_vote,
+    int tid = threadIdx.x)
 {
 #pragma clang fp contract(off)
-    const int tid = threadIdx.x;
     if (tid >= tend) return;
     const int t = t0 + tid;
     const int base = tid + BT_HALO;
@@ -273,7 +291,11 @@ __device__ inline void bt_shared_votes(
     const float sma50 = (float)(s50 / (double)L50);
     const int trend = (cl > sma20 && sma20 > sma50) ? 1
                       : ((cl < sma20 && sma20 < sma50) ? -1 : 0);
-    sh_vote[tid] = make_float4(
+    if (RECORD)
+        sh_vote[2 * tid] = make_float4(
+            cl, hl[base][0], hl[base][1],
+            (t == 0) ? 0.0f : cl - chist[base - 1]);
+    sh_vote[RECORD ? 2 * tid + 1 : tid] = make_float4(
         100.0f * (cl - lmin), -100.0f * (hmax - cl),
         fmaxf(hmax - lmin, BT_EPS), __int_as_float(trend));
 }
