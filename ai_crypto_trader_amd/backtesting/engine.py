@@ -114,6 +114,7 @@ class BacktestEngine:
         self.results_dir = Path(data_dir) / "results"
         self.results_dir.mkdir(parents=True, exist_ok=True)
         self.last_saved: Path | None = None      # newest results JSON
+        self.last_candles: np.ndarray | None = None   # of the newest run
 
     # --- single run ------------------------------------------------------
     def run_backtest(self, symbol: str, strategy: str = "default",
@@ -131,6 +132,7 @@ class BacktestEngine:
         df = self.dm.load_market_data(symbol, interval,
                                       n_candles=n_candles)
         candles = self.dm.to_chlv(df.iloc[:n_candles])
+        self.last_candles = candles     # (1, T, 4), for per-candle labels
         fam = FAMILIES.get(strategy)
         if fam is not None:
             vec = fam.clip(fam.dict_to_params(params or {})[None])

@@ -139,6 +139,82 @@ def generate_condition_market(condition: str, n_candles: int = 5000,
     return candles_chl_v(generate_ohlcv(n_candles, 1, seed=seed, **params))
 
 
+def label_regimes(candles: np.ndarray, method: str = "hmm",
+                  n_regimes: int = 4, win: int = 32, seed: int = 0,
+                  device: str | None = None) -> np.ndarray:
+    """Detected regime of every candle: (nsym, T, 4) candles -> (nsym, T)
+    int8 indices into services.market_regime.REGIMES, -1 for the first
+    `win` candles. Runs the regime stack (window features, per-symbol
+    standardisation, `method` in hmm | kmeans | gmm, the cluster -> regime
+    heuristic) on the close column, on `device` when it is a cuda device.
+    Candle t takes the label of the window ending at t - 1, so no label
+    uses candle t's own close."""
+    import torch
+
+    from ..ops.regime import regime_features_cpu, regime_features_gpu
+    from ..services.market_regime import (
+        REGIMES, cluster_many, label_clusters, standardize_many,
+    )
+
+    closes = np.ascontiguousarray(np.asarray(candles)[:, :, 0], np.float32)
+    nsym, T = closes.shape
+    labels = np.full((nsym, T), -1, np.int8)
+    n = T - win
+    if n < max(4 * n_regimes, 2):
+        raise ValueError(
+            f"label_regimes: {T} candles give {max(n, 0)} windows of "
+            f"{win}, fewer than the {4 * n_regimes} that {n_regimes} "
+            "regimes need")
+    if device is not None and str(device).startswith("cuda"):
+        feats = regime_features_gpu(torch.from_numpy(closes).to(device),
+                                    None, win)
+    else:
+        feats = torch.from_numpy(regime_features_cpu(closes, None, win))
+    nwin = torch.full((nsym,), n, dtype=torch.int32, device=feats.device)
+    assign, _, _ = cluster_many(standardize_many(feats, nwin), nwin, method,
+                                n_regimes, seed)
+    feats_np = feats.cpu().numpy()
+    for s in range(nsym):
+        names = label_clusters(feats_np[s], assign[s], n_regimes)
+        lut = np.asarray([REGIMES.index(names[c])
+                          for c in range(n_regimes)], np.int8)
+        labels[s, win:] = lut[assign[s, :n]]
+    return labels
+
+
+def regime_breakdown(ledger, labels: np.ndarray, p: int = 0) -> dict:
+    """Closed trades of strategy `p` over every symbol of `ledger`
+    (backtesting/ledger.py), bucketed by the regime label at entry_t:
+    {regime: {n_trades, win_rate, pnl, avg_pnl, share_of_candles}} for
+    every name in REGIMES plus "unlabelled" (label -1: entries before the
+    first window is complete)."""
+    from ..services.market_regime import REGIMES
+
+    led = ledger.numpy()
+    labels = np.asarray(labels)
+    names = list(REGIMES) + ["unlabelled"]
+    pnls: dict[str, list] = {nm: [] for nm in names}
+    for s in range(labels.shape[0]):
+        k = led.n_kept(p, s)
+        closed = led.exit_t[p, s, :k] >= 0
+        lab = labels[s, led.entry_t[p, s, :k][closed]]
+        pnl = led.pnl[p, s, :k][closed].astype(np.float64)
+        for r, nm in enumerate(names):
+            pnls[nm].append(pnl[lab == (r if r < len(REGIMES) else -1)])
+    out = {}
+    for r, nm in enumerate(names):
+        x = np.concatenate(pnls[nm]) if pnls[nm] else np.zeros(0)
+        share = float((labels == (r if r < len(REGIMES) else -1)).mean())
+        out[nm] = {
+            "n_trades": int(len(x)),
+            "win_rate": float((x > 0).mean()) if len(x) else 0.0,
+            "pnl": float(x.sum()),
+            "avg_pnl": float(x.mean()) if len(x) else 0.0,
+            "share_of_candles": share,
+        }
+    return out
+
+
 class StrategyEvaluationSystem:
     """K-fold time-series CV + per-condition evaluation + comparison."""
 
@@ -190,6 +266,44 @@ class StrategyEvaluationSystem:
             m = self._run(mkt, vec)
             out[cond] = metrics_to_stats(m[0, 0], mkt.shape[1])
         return out
+
+    def evaluate_by_regime(self, candles: np.ndarray, strategy_params: dict,
+                           method: str = "hmm", n_regimes: int = 4,
+                           win: int = 32, seed: int = 0,
+                           use_gpu: bool | None = None,
+                           labels: np.ndarray | None = None,
+                           max_trades: int | None = None) -> dict:
+        """Performance attributed to DETECTED regimes
+        (market_regime_service.py:829 update_strategy_performance_by_
+        regime): label every candle (label_regimes, or the `labels`
+        given), run the vote backtest with its trade ledger, and bucket
+        the closed trades by the label at entry (regime_breakdown).
+        use_gpu (default: this system's device is cuda) takes the HIP
+        ledger and feature/HMM kernels, otherwise their numpy twins."""
+        from .ledger import DEFAULT_MAX_TRADES
+
+        if use_gpu is None:
+            use_gpu = self.device.startswith("cuda")
+        dev = (self.device if self.device.startswith("cuda") else "cuda:0") \
+            if use_gpu else None
+        candles = np.ascontiguousarray(candles, np.float32)
+        if labels is None:
+            labels = label_regimes(candles, method, n_regimes, win, seed,
+                                   device=dev)
+        vec = clip_params(dict_to_params(strategy_params)[None])
+        max_trades = max_trades or DEFAULT_MAX_TRADES
+        if use_gpu:
+            import torch
+
+            from ..ops.backtest import run_backtest_ledger_gpu
+            ledger = run_backtest_ledger_gpu(
+                torch.from_numpy(candles).to(dev),
+                torch.from_numpy(vec).to(dev), max_trades=max_trades)
+            torch.cuda.synchronize()
+        else:
+            ledger = run_backtest_cpu(candles, vec, record_trades=True,
+                                      max_trades=max_trades)
+        return regime_breakdown(ledger, labels)
 
     def compare_strategies(self, strategies: dict[str, dict],
                            candles: np.ndarray) -> dict:

@@ -125,6 +125,20 @@ class ResultAnalyzer:
             "avg_loss": float(losses.mean()) if len(losses) else 0.0,
             "expectancy": float(pnl.mean()) if len(pnl) else 0.0,
         })
+        if "regime_at_entry" in stats:
+            # parallel to stats["trades"]: the detected regime at entry_t
+            by_regime = {}
+            for t, reg in zip(stats["trades"], stats["regime_at_entry"]):
+                if t["reason"] == "open":
+                    continue
+                r = by_regime.setdefault(
+                    reg, {"count": 0, "pnl": 0.0, "wins": 0})
+                r["count"] += 1
+                r["pnl"] += t["pnl"]
+                r["wins"] += t["pnl"] > 0
+            for r in by_regime.values():
+                r["win_rate"] = r.pop("wins") / r["count"]
+            out["by_regime"] = by_regime
         return out
 
     def plot_trade_analysis(self, stats: dict, fname: str | None = None):

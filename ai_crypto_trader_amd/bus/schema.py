@@ -67,6 +67,7 @@ class Keys:
     MONTE_CARLO_REQUEST = "monte_carlo_request"        # :783
     MARKET_REGIME_HISTORY = "market_regime_history"
     CURRENT_MARKET_REGIME = "current_market_regime"    # strategy_evolution:262
+    MARKET_REGIMES = "market_regimes"                  # {symbol: entry}
     STRATEGY_PARAMS = "strategy_params"                # :353
     SOCIAL_RISK_ADJUSTMENTS = "social_risk_adjustments"
     SOCIAL_RISK_REPORT = "social_risk_report"

@@ -98,6 +98,7 @@ class RegimeConfig(BaseModel):
     n_regimes: int = 4
     lookback: int = 500
     retrain_interval_s: float = 3600.0
+    per_symbol: bool = False                  # also publish market_regimes
 
 
 class GridConfig(BaseModel):

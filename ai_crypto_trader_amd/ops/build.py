@@ -32,6 +32,7 @@ SOURCES = [
     "gru.hip",
     "attention.hip",
     "laggedcorr.hip",
+    "regime.hip",
     "histogram.hip",
     "rl_env.hip",
     "rng_probe.hip",

@@ -91,6 +91,17 @@ extern "C" void launch_attn_bwd(const void*, const void*, const void*,
                                 void*, long, int, int, float, hipStream_t);
 extern "C" void launch_lagged_corr(const float*, const float*, float*, int,
                                    int, hipStream_t);
+extern "C" void launch_regime_features(const float*, const int*, float*, int,
+                                       int, int, hipStream_t);
+extern "C" void launch_hmm_estep(const float*, const int*, const float*,
+                                 const float*, const float*, const float*,
+                                 float*, float*, float*, float*, float*,
+                                 float*, float*, float*, float*, float*, int,
+                                 int, int, int, hipStream_t);
+extern "C" void launch_hmm_viterbi(const float*, const int*, const float*,
+                                   const float*, const float*, const float*,
+                                   unsigned char*, int*, int, int, int, int,
+                                   hipStream_t);
 extern "C" void launch_vp_hist(const float*, const float*, const float*,
                                float*, float*, int, int, int, hipStream_t);
 extern "C" void launch_env_reset(const float*, float*, float*, int, int, int,
@@ -549,6 +560,62 @@ PYBIND11_MODULE(_hip_ops, m) {
                              reinterpret_cast<float*>(updown), nsym, T,
                              n_bins, as_stream(stream));
               check(hipGetLastError(), "vp_hist launch");
+          });
+
+    // Market-regime stack (ops/hip/regime.hip, ops/regime.py). Limits are
+    // checked here, before any launch.
+    m.def("regime_features",
+          [](uintptr_t closes, uintptr_t lengths, uintptr_t out, int S,
+             int Tmax, int win, uintptr_t stream) {
+              if (win < 2 || win > 256)
+                  throw std::runtime_error(
+                      "regime_features: win must be in [2, 256], got " +
+                      std::to_string(win));
+              launch_regime_features(reinterpret_cast<const float*>(closes),
+                                     reinterpret_cast<const int*>(lengths),
+                                     reinterpret_cast<float*>(out), S, Tmax,
+                                     win, as_stream(stream));
+              check(hipGetLastError(), "regime_features launch");
+          });
+
+    m.def("hmm_estep",
+          [](uintptr_t X, uintptr_t lengths, uintptr_t mu, uintptr_t var,
+             uintptr_t logA, uintptr_t logpi, uintptr_t alpha_ws,
+             uintptr_t c_ws, uintptr_t ll, uintptr_t gamma0,
+             uintptr_t gamma_sum, uintptr_t gamma_head, uintptr_t xi_sum,
+             uintptr_t sx, uintptr_t sxx, uintptr_t gamma, int B, int Tmax,
+             int K, int F, uintptr_t stream) {
+              if (K < 1 || K > 8 || F < 1 || F > 8)
+                  throw std::runtime_error(
+                      "hmm_estep: needs 1 <= K <= 8 and 1 <= F <= 8, got K=" +
+                      std::to_string(K) + " F=" + std::to_string(F));
+              auto f = [](uintptr_t p) { return reinterpret_cast<float*>(p); };
+              launch_hmm_estep(f(X), reinterpret_cast<const int*>(lengths),
+                               f(mu), f(var), f(logA), f(logpi), f(alpha_ws),
+                               f(c_ws), f(ll), f(gamma0), f(gamma_sum),
+                               f(gamma_head), f(xi_sum), f(sx), f(sxx),
+                               f(gamma), B, Tmax, K, F, as_stream(stream));
+              check(hipGetLastError(), "hmm_estep launch");
+          });
+
+    m.def("hmm_viterbi",
+          [](uintptr_t X, uintptr_t lengths, uintptr_t mu, uintptr_t var,
+             uintptr_t logA, uintptr_t logpi, uintptr_t bp_ws,
+             uintptr_t path, int B, int Tmax, int K, int F,
+             uintptr_t stream) {
+              if (K < 1 || K > 8 || F < 1 || F > 8)
+                  throw std::runtime_error(
+                      "hmm_viterbi: needs 1 <= K <= 8 and 1 <= F <= 8, got "
+                      "K=" + std::to_string(K) + " F=" + std::to_string(F));
+              auto f = [](uintptr_t p) {
+                  return reinterpret_cast<const float*>(p);
+              };
+              launch_hmm_viterbi(f(X), reinterpret_cast<const int*>(lengths),
+                                 f(mu), f(var), f(logA), f(logpi),
+                                 reinterpret_cast<unsigned char*>(bp_ws),
+                                 reinterpret_cast<int*>(path), B, Tmax, K, F,
+                                 as_stream(stream));
+              check(hipGetLastError(), "hmm_viterbi launch");
           });
 
     m.def("device_synchronize", []() { check(hipDeviceSynchronize(), "sync"); });

@@ -8,7 +8,12 @@ cluster->label
 mapping by mean return & volatility (:226-296), plus the rule-based
 fallback (market_regime_service.py:503-604). Publishes `strategy_switch`
 on regime changes; maintains `current_market_regime` /
-`market_regime_history` keys."""
+`market_regime_history` keys.
+
+For the whole universe: `detect_many` runs the features, the HMM's
+Baum-Welch and Viterbi for every symbol at once (kmeans_many,
+GaussianHMMBatched over ops/regime.py's HIP kernels or their numpy twins);
+with `regime.per_symbol` the loop also maintains `market_regimes`."""
 
 from __future__ import annotations
 
@@ -190,6 +195,156 @@ class GaussianHMMTorch:
         return path
 
 
+def kmeans_many(X: torch.Tensor, lengths, k: int = 4, iters: int = 20,
+                seed: int = 0) -> torch.Tensor:
+    """KMeansTorch for B padded sequences at once: X (B, N, F), lengths
+    (B,) -> centres (B, k, F). Seeded per sequence like KMeansTorch
+    (randperm(n) from a CPU generator at `seed`); an empty cluster keeps
+    its centre. Every sequence needs at least k rows."""
+    B, N, F = X.shape
+    lengths = torch.as_tensor(lengths, device=X.device).long()
+    assert int(lengths.min()) >= k, "kmeans_many: a sequence has < k rows"
+    idx = torch.stack([
+        torch.randperm(int(n), generator=torch.Generator(
+            device="cpu").manual_seed(seed))[:k]
+        for n in lengths.tolist()]).to(X.device)                  # (B, k)
+    centers = torch.gather(X, 1, idx[:, :, None].expand(B, k, F)).clone()
+    valid = torch.arange(N, device=X.device)[None] < lengths[:, None]
+    for _ in range(iters):
+        assign = torch.cdist(X, centers).argmin(dim=2)            # (B, N)
+        onehot = (torch.nn.functional.one_hot(assign, k)
+                  * valid[:, :, None]).to(X.dtype)                # (B, N, k)
+        count = onehot.sum(1)                                     # (B, k)
+        mean = (onehot.transpose(1, 2) @ X) / count.clamp(min=1)[:, :, None]
+        centers = torch.where((count > 0)[:, :, None], mean, centers)
+    return centers
+
+
+class GaussianHMMBatched:
+    """GaussianHMMTorch for B sequences at once: the same init (KMeans
+    centres, global variance, sticky 0.95 transitions) and M-step, with the
+    E-step and Viterbi as one HIP launch each on cuda tensors
+    (ops/regime.py::hmm_estep_gpu / hmm_viterbi_gpu) and their numpy twins
+    otherwise. Parameters are per sequence: mu, var (B, k, F), logA
+    (B, k, k), logpi (B, k); `ll_history` holds the (B,) log-likelihood
+    of every EM iteration."""
+
+    def __init__(self, k: int = 4, iters: int = 30, seed: int = 0):
+        self.k = k
+        self.iters = iters
+        self.seed = seed
+        self.ll_history: list[np.ndarray] = []
+
+    def _params(self):
+        return self.mu, self.var, self.logA, self.logpi
+
+    @staticmethod
+    def _lengths(X, lengths):
+        if lengths is None:
+            return torch.full((X.shape[0],), X.shape[1], dtype=torch.int32,
+                              device=X.device)
+        return torch.as_tensor(lengths, device=X.device).to(torch.int32)
+
+    def _estep(self, X, lengths, want_gamma=False) -> dict:
+        from ..ops.regime import hmm_estep_cpu, hmm_estep_gpu
+
+        if X.is_cuda:
+            return hmm_estep_gpu(X, lengths, *self._params(),
+                                 want_gamma=want_gamma)
+        st = hmm_estep_cpu(X.numpy(), lengths.numpy(),
+                           *(p.numpy() for p in self._params()),
+                           want_gamma=want_gamma)
+        return {key: torch.from_numpy(np.ascontiguousarray(v))
+                for key, v in st.items()}
+
+    def init_params(self, X: torch.Tensor, lengths):
+        B, N, F = X.shape
+        k = self.k
+        valid = (torch.arange(N, device=X.device)[None]
+                 < lengths[:, None])[:, :, None].to(X.dtype)
+        n = lengths.to(X.dtype)[:, None]
+        mean = (X * valid).sum(1) / n
+        var = (((X - mean[:, None]) ** 2) * valid).sum(1) \
+            / (n - 1).clamp(min=1)
+        self.mu = kmeans_many(X, lengths, k, 20, self.seed)
+        self.var = torch.clamp(var[:, None, :].expand(B, k, F), min=1e-6)
+        self.var = self.var.contiguous()
+        if k > 1:
+            A = torch.full((k, k), 0.05 / (k - 1), device=X.device,
+                           dtype=X.dtype).fill_diagonal_(0.95)
+        else:
+            A = torch.ones(1, 1, device=X.device, dtype=X.dtype)
+        self.logA = torch.log(A)[None].expand(B, k, k).contiguous()
+        self.logpi = torch.full((B, k), -float(np.log(k)), device=X.device,
+                                dtype=X.dtype)
+
+    def fit_many(self, X: torch.Tensor, lengths=None):
+        """X (B, Tmax, F), lengths (B,): Baum-Welch for every sequence."""
+        from ..ops.regime import hmm_mstep
+
+        lengths = self._lengths(X, lengths)
+        self.init_params(X, lengths)
+        self.ll_history = []
+        for _ in range(self.iters):
+            st = self._estep(X, lengths)
+            self.ll_history.append(st["ll"].cpu().numpy().copy())
+            p = hmm_mstep(st)
+            self.mu, self.var = p["mu"].to(X.dtype), p["var"].to(X.dtype)
+            self.logA = p["logA"].to(X.dtype)
+            self.logpi = p["logpi"].to(X.dtype)
+        return self
+
+    def predict_many(self, X: torch.Tensor, lengths=None) -> torch.Tensor:
+        """Viterbi paths (B, Tmax), -1 past lengths[b]."""
+        from ..ops.regime import hmm_viterbi_cpu, hmm_viterbi_gpu
+
+        lengths = self._lengths(X, lengths)
+        if X.is_cuda:
+            return hmm_viterbi_gpu(X, lengths, *self._params())
+        return torch.from_numpy(hmm_viterbi_cpu(
+            X.numpy(), lengths.numpy(),
+            *(p.numpy() for p in self._params())))
+
+    def posterior_many(self, X: torch.Tensor, lengths=None) -> torch.Tensor:
+        """State posteriors gamma (B, Tmax, k), 0 past lengths[b]."""
+        return self._estep(X, self._lengths(X, lengths),
+                           want_gamma=True)["gamma"]
+
+    def log_likelihood(self, X: torch.Tensor, lengths=None) -> torch.Tensor:
+        return self._estep(X, self._lengths(X, lengths))["ll"]
+
+
+def standardize_many(feats: torch.Tensor, nwin: torch.Tensor) -> torch.Tensor:
+    """Per-sequence (x - mean) / (std + 1e-9) over each sequence's first
+    nwin[b] rows, as `detect` standardises one symbol; padding rows are 0."""
+    valid = (torch.arange(feats.shape[1], device=feats.device)[None]
+             < nwin[:, None])[:, :, None].to(feats.dtype)
+    n = nwin.to(feats.dtype)[:, None]
+    mean = (feats * valid).sum(1) / n
+    std = ((((feats - mean[:, None]) ** 2) * valid).sum(1)
+           / (n - 1).clamp(min=1)).sqrt()
+    return ((feats - mean[:, None]) / (std[:, None] + 1e-9)) * valid
+
+
+def cluster_many(Xn: torch.Tensor, nwin: torch.Tensor, method: str, k: int,
+                 seed: int):
+    """Cluster every sequence of Xn (B, N, F): -> (assign (B, N) numpy,
+    -1 past nwin[b]; posteriors (B, N, k) numpy for `hmm`, else None; the
+    model). `hmm` is one batched model; `kmeans` / `gmm` loop the
+    per-symbol classes."""
+    if method == "hmm":
+        model = GaussianHMMBatched(k, seed=seed).fit_many(Xn, nwin)
+        return (model.predict_many(Xn, nwin).cpu().numpy(),
+                model.posterior_many(Xn, nwin).cpu().numpy(), model)
+    assign = np.full(Xn.shape[:2], -1, np.int64)
+    model = None
+    for i, m in enumerate(nwin.tolist()):
+        cls = GMMTorch if method == "gmm" else KMeansTorch
+        model = cls(k, seed=seed).fit(Xn[i, :m])
+        assign[i, :m] = model.predict(Xn[i, :m]).cpu().numpy()
+    return assign, None, model
+
+
 def label_clusters(X: np.ndarray, assign: np.ndarray, k: int) -> dict:
     """Heuristic cluster -> regime mapping by mean return & volatility
     (market_regime_detector.py:226-296)."""
@@ -341,6 +496,58 @@ class MarketRegimeService(Service):
         conf = float((assign == assign[-1]).mean())
         return regime, conf
 
+    def detect_many(self, closes_by_symbol: dict) -> dict:
+        """`detect` for a universe: {symbol: closes} -> {symbol: (regime,
+        confidence)}. Features come from one batched pass; `hmm` fits and
+        decodes every symbol in one batched model (GaussianHMMBatched) and
+        takes as confidence the posterior of the Viterbi state at the last
+        step; `kmeans` / `gmm` run the per-symbol classes over the batched
+        features. Symbols `detect` would hand to the rules get the rules
+        here too."""
+        from ..ops.regime import regime_features_cpu, regime_features_gpu
+
+        method = self.config.regime.method
+        k = self.config.regime.n_regimes
+        win = 32
+        out, todo = {}, []
+        for sym, closes in closes_by_symbol.items():
+            closes = np.asarray(closes, np.float64)
+            if method == "rf" and len(closes) >= 200:
+                out[sym] = self.detect(closes)
+            elif (method == "rule" or len(closes) < 200
+                  or len(closes) - win < 4 * k):
+                out[sym] = rule_based_regime(closes)
+            else:
+                todo.append((sym, closes))
+        if not todo:
+            return out
+        S = len(todo)
+        lens = np.asarray([len(c) for _, c in todo], np.int32)
+        padded = np.ones((S, int(lens.max())), np.float32)
+        for i, (_, c) in enumerate(todo):
+            padded[i, :len(c)] = c
+        if self.device != "cpu":
+            feats = regime_features_gpu(
+                torch.from_numpy(padded).to(self.device),
+                torch.from_numpy(lens).to(self.device), win)
+        else:
+            feats = torch.from_numpy(regime_features_cpu(padded, lens, win))
+        nwin = torch.from_numpy(lens - win).to(feats.device)
+        paths, post, self.model = cluster_many(
+            standardize_many(feats, nwin), nwin, method, k,
+            self.config.seed)
+        feats_np = feats.cpu().numpy()
+        for i, (sym, _) in enumerate(todo):
+            m = int(lens[i]) - win
+            assign = paths[i, :m]
+            if post is not None:
+                conf = float(post[i, m - 1, assign[-1]])
+            else:
+                conf = float((assign == assign[-1]).mean())
+            labels = label_clusters(feats_np[i, :m], assign, k)
+            out[sym] = (labels.get(int(assign[-1]), "ranging"), conf)
+        return {sym: out[sym] for sym in closes_by_symbol}
+
     async def _regime_loop(self):
         while self.running:
             closes = self._primary_closes()
@@ -366,7 +573,41 @@ class MarketRegimeService(Service):
                                        f"for-{regime}",
                                        "regime change").to_dict())
                     self.current = regime
+            if self.config.regime.per_symbol:
+                await self._publish_per_symbol()
             await self.sleep(5.0)
+
+    async def _publish_per_symbol(self):
+        """`market_regimes`: {symbol: entry} for every tracked symbol with
+        enough history, next to the primary symbol's keys. An entry says
+        which method produced it: the configured one, or "rule" when
+        detect_many failed and the rules stood in. A missing HIP extension
+        on a GPU device is not such a failure: it raises."""
+        if self.device != "cpu":
+            from ..ops import require_hip_ops
+            require_hip_ops()
+        lookback = self.config.regime.lookback
+        universe = {sym: np.asarray(h[-lookback:], np.float64)
+                    for sym, h in self.prices.items() if len(h) >= 64}
+        if not universe:
+            return
+        method = self.config.regime.method
+        try:
+            found = self.detect_many(universe)
+        except Exception as e:
+            self.log.warning("detect_many failed, rules for all: %s", e)
+            found = {sym: rule_based_regime(c) for sym, c in universe.items()}
+            method = "rule"
+        now = time.time()
+        entries = {}
+        for sym, (regime, conf) in found.items():
+            c = universe[sym]
+            vol = float(np.diff(np.log(c[-100:])).std()
+                        * np.sqrt(525_600)) if len(c) > 2 else 0.0
+            entries[sym] = {"regime": regime, "confidence": conf,
+                            "volatility": min(vol, 2.0), "at": now,
+                            "method": method}
+        await self.bus.set(Keys.MARKET_REGIMES, entries)
 
     async def run(self):
         pass

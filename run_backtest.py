@@ -62,6 +62,10 @@ def main():
                    help="record the trade ledger (vote machine): print "
                         "the per-exit-reason table and write a "
                         "*_trades.csv next to the saved JSON")
+    b.add_argument("--by-regime", action="store_true",
+                   help="with --trades: label the history with the regime "
+                        "detector (HMM) and print the closed trades split "
+                        "by the regime at entry")
     b.add_argument("--max-trades", type=int, default=DEFAULT_MAX_TRADES,
                    help="trade records kept (the newest are dropped)")
     b.add_argument("--equity-stride", type=int, default=1,
@@ -88,6 +92,8 @@ def main():
                          "total_return, win_rate, profit_factor")
 
     args = ap.parse_args()
+    if getattr(args, "by_regime", False) and not args.trades:
+        ap.error("--by-regime splits the trade ledger: it needs --trades")
     dm = HistoricalDataManager(args.data_dir)
 
     if args.cmd == "fetch":
@@ -120,6 +126,24 @@ def main():
         print(json.dumps(stats, indent=2, default=str))
         if trades is not None:
             stats["trades"] = trades
+            if args.by_regime:
+                from ai_crypto_trader_amd.backtesting.evaluation import (
+                    label_regimes,
+                )
+                from ai_crypto_trader_amd.services.market_regime import (
+                    REGIMES,
+                )
+                try:
+                    labels = label_regimes(
+                        eng.last_candles,
+                        device=eng.device if eng.device.startswith("cuda")
+                        else None)[0]
+                except ValueError as e:
+                    raise SystemExit(f"--by-regime: {e}")
+                stats["regime_at_entry"] = [
+                    REGIMES[labels[t["entry_t"]]]
+                    if labels[t["entry_t"]] >= 0 else "unlabelled"
+                    for t in trades]
             ta = ra.trade_analysis(stats)
             print(f"{'exit reason':<14} {'count':>6} {'pnl':>12}")
             for r in REASONS[1:]:
@@ -128,6 +152,14 @@ def main():
             print(f"{'closed':<14} {ta['n_closed']:>6} "
                   f"{ta['realized_pnl']:>12.6f}   open {ta['n_open']}, "
                   f"kept {len(trades)} of {stats['n_records']} records")
+            if args.by_regime:
+                print(f"{'regime at entry':<16} {'count':>6} "
+                      f"{'win rate':>9} {'pnl':>12}")
+                for r in [*REGIMES, "unlabelled"]:
+                    row = ta["by_regime"].get(
+                        r, {"count": 0, "win_rate": 0.0, "pnl": 0.0})
+                    print(f"{r:<16} {row['count']:>6} "
+                          f"{row['win_rate']:>9.3f} {row['pnl']:>12.6f}")
             path = eng.last_saved.with_name(
                 eng.last_saved.stem + "_trades.csv")
             with open(path, "w", newline="") as f:
