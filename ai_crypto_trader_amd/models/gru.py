@@ -7,80 +7,41 @@ import torch
 import torch.nn as nn
 
 from ..ops import require_hip_ops
+from ._recurrent import hh_grads, launch_fwd, pad_batch
 
 
 class _FusedGRUSeq(torch.autograd.Function):
     @staticmethod
     def forward(ctx, xproj: torch.Tensor, w_hh: torch.Tensor,
                 b_hh: torch.Tensor):
-        ops = require_hip_ops()
-        T, B, three_h = xproj.shape
-        H = three_h // 3
-        dev = xproj.device
-        w_bf = w_hh.to(torch.bfloat16).contiguous()          # (H, 3H)
-        wt_bf = w_bf.t().contiguous()                        # (3H, H)
-        bias = b_hh.float().contiguous()
-        h_out = torch.empty((T, B, H), dtype=torch.bfloat16, device=dev)
-        gates = torch.empty((T, B, three_h), dtype=torch.bfloat16,
-                            device=dev)
-        hpn = torch.empty((T, B, H), dtype=torch.float32, device=dev)
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        ops.gru_seq_fwd(
-            xproj.contiguous().data_ptr(), wt_bf.data_ptr(),
-            bias.data_ptr(), h_out.data_ptr(), gates.data_ptr(),
-            hpn.data_ptr(), B, T, H, 1, stream,
-        )
+        h_out, gates, hpn, w_bf = launch_fwd(
+            require_hip_ops().gru_seq_fwd, xproj, w_hh, b_hh, 3, save=True)
         ctx.save_for_backward(gates, hpn, h_out, w_bf)
-        ctx.dims = (T, B, H)
         return h_out
 
     @staticmethod
     def backward(ctx, grad_h: torch.Tensor):
-        ops = require_hip_ops()
         gates, hpn, h_out, w_bf = ctx.saved_tensors
-        T, B, H = ctx.dims
+        T, B, H = h_out.shape
         dev = grad_h.device
-        dgates_x = torch.empty((T, B, 3 * H), dtype=torch.bfloat16,
-                               device=dev)
+        dgates_x = torch.empty_like(gates)
         dh_up = grad_h.float().contiguous()
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        ops.gru_seq_bwd(
+        require_hip_ops().gru_seq_bwd(
             dh_up.data_ptr(), gates.data_ptr(), hpn.data_ptr(),
-            h_out.data_ptr(), w_bf.contiguous().data_ptr(),
-            dgates_x.data_ptr(), B, T, H, stream,
+            h_out.data_ptr(), w_bf.data_ptr(), dgates_x.data_ptr(), B, T, H,
+            torch.cuda.current_stream(dev).cuda_stream,
         )
-        # h-side dgates: the n-column is da_n * r (gru.hip header).
-        # All bf16: the weight-grad GEMM accumulates f32 inside hipBLASLt
-        # (autocast semantics), no f32 materialization of dgates
+        # h-side dgates: the n-column is da_n * r (gru.hip header), in bf16
         dg_h = dgates_x.clone()
         dg_h[..., 2 * H:] = dg_h[..., 2 * H:] * gates[..., :H]
-        h_prev = torch.cat(
-            [torch.zeros((1, B, H), dtype=h_out.dtype, device=dev),
-             h_out[:-1]], dim=0,
-        )
-        dg = dg_h.reshape(T * B, 3 * H)
-        dw_hh = (h_prev.reshape(T * B, H).t() @ dg).float()
-        db_hh = dg.sum(dim=0, dtype=torch.float32)
-        return dgates_x, dw_hh, db_hh
+        return (dgates_x, *hh_grads(h_out, dg_h, time_dim=0))
 
 
 def gru_seq_infer(xproj: torch.Tensor, w_hh: torch.Tensor,
                   b_hh: torch.Tensor) -> torch.Tensor:
-    """Inference-only fused forward: skips the backward-save stores
-    (gates/hpn), ~4x fewer global writes per cell — the serving path
-    (mirrors lstm_seq_infer)."""
-    ops = require_hip_ops()
-    T, B, three_h = xproj.shape
-    H = three_h // 3
-    dev = xproj.device
-    wt_bf = w_hh.detach().to(torch.bfloat16).t().contiguous()
-    bias = b_hh.detach().float().contiguous()
-    h_out = torch.empty((T, B, H), dtype=torch.bfloat16, device=dev)
-    stream = torch.cuda.current_stream(dev).cuda_stream
-    ops.gru_seq_fwd(xproj.contiguous().data_ptr(), wt_bf.data_ptr(),
-                    bias.data_ptr(), h_out.data_ptr(), 0, 0, B, T, H, 0,
-                    stream)
-    return h_out
+    """Inference-only fused forward (no backward saves): the serving path."""
+    return launch_fwd(require_hip_ops().gru_seq_fwd, xproj, w_hh, b_hh, 3,
+                      save=False)
 
 
 class FusedGRULayer(nn.Module):
@@ -102,17 +63,14 @@ class FusedGRULayer(nn.Module):
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         if x.is_cuda:
-            T, B, _ = x.shape
-            pad = (-B) % 64
-            if pad:
-                x = torch.cat([x, x.new_zeros(T, pad, x.shape[2])], dim=1)
+            x, unpad = pad_batch(x, 1)
             bf = torch.bfloat16    # f32 master weights, bf16 GEMMs
             xproj = (x.to(bf) @ self.w_ih.to(bf) + self.b_ih.to(bf))
             if torch.is_grad_enabled():
                 h = _FusedGRUSeq.apply(xproj, self.w_hh, self.b_hh)
             else:    # serving path: no backward saves
                 h = gru_seq_infer(xproj, self.w_hh, self.b_hh)
-            return h[:, :B] if pad else h
+            return unpad(h)
         return self._forward_reference(x)
 
     def _forward_reference(self, x: torch.Tensor) -> torch.Tensor:

@@ -18,6 +18,7 @@ import torch
 import torch.nn as nn
 
 from ..ops import require_hip_ops
+from ._recurrent import hh_grads, launch_fwd, pad_batch
 
 
 class _FusedLSTMSeq(torch.autograd.Function):
@@ -30,72 +31,32 @@ class _FusedLSTMSeq(torch.autograd.Function):
     @staticmethod
     def forward(ctx, xproj: torch.Tensor, w_hh: torch.Tensor,
                 b_hh: torch.Tensor):
-        ops = require_hip_ops()
-        T, B, four_h = xproj.shape
-        H = four_h // 4
-        assert xproj.dtype == torch.bfloat16 and xproj.is_cuda
-        dev = xproj.device
-        w_bf = w_hh.to(torch.bfloat16).contiguous()           # (H, 4H)
-        wt_bf = w_bf.t().contiguous()                         # (4H, H)
-        bias = b_hh.float().contiguous()
-        h_out = torch.empty((T, B, H), dtype=torch.bfloat16, device=dev)
-        gates = torch.empty((T, B, four_h), dtype=torch.bfloat16, device=dev)
-        c_sav = torch.empty((T, B, H), dtype=torch.float32, device=dev)
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        ops.lstm_seq_fwd(
-            xproj.contiguous().data_ptr(), wt_bf.data_ptr(), bias.data_ptr(),
-            h_out.data_ptr(), gates.data_ptr(), c_sav.data_ptr(), B, T, H,
-            1, stream,
-        )
+        h_out, gates, c_sav, w_bf = launch_fwd(
+            require_hip_ops().lstm_seq_fwd, xproj, w_hh, b_hh, 4, save=True)
         ctx.save_for_backward(gates, c_sav, h_out, w_bf)
-        ctx.dims = (T, B, H)
         return h_out
-
 
     @staticmethod
     def backward(ctx, grad_h: torch.Tensor):
-        ops = require_hip_ops()
         gates, c_sav, h_out, w_bf = ctx.saved_tensors
-        T, B, H = ctx.dims
+        T, B, H = h_out.shape
         dev = grad_h.device
-        dgates = torch.empty((T, B, 4 * H), dtype=torch.bfloat16, device=dev)
+        dgates = torch.empty_like(gates)
         dh_up = grad_h.float().contiguous()
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        ops.lstm_seq_bwd(
+        require_hip_ops().lstm_seq_bwd(
             dh_up.data_ptr(), gates.data_ptr(), c_sav.data_ptr(),
-            w_bf.contiguous().data_ptr(), dgates.data_ptr(), B, T, H, stream,
+            w_bf.data_ptr(), dgates.data_ptr(), B, T, H,
+            torch.cuda.current_stream(dev).cuda_stream,
         )
-        # dW_hh = sum_t h_{t-1}^T dgates_t — one hipBLASLt bf16 GEMM
-        # (f32 accumulation inside, bf16 grad out = torch.autocast
-        # semantics; the f32 materialization of dgates was 1 GB/step)
-        h_prev = torch.cat(
-            [torch.zeros((1, B, H), dtype=h_out.dtype, device=dev),
-             h_out[:-1]], dim=0,
-        )
-        dg = dgates.reshape(T * B, 4 * H)
-        dw_hh = (h_prev.reshape(T * B, H).t() @ dg).float()
-        db_hh = dg.sum(dim=0, dtype=torch.float32)
-        return dgates, dw_hh, db_hh
-
+        return (dgates, *hh_grads(h_out, dgates, time_dim=0))
 
 
 def lstm_seq_infer(xproj: torch.Tensor, w_hh: torch.Tensor,
                    b_hh: torch.Tensor) -> torch.Tensor:
-    """Inference-only fused forward: skips the backward-save stores
-    (gates/c), ~5x fewer global writes per cell — the serving path."""
-    ops = require_hip_ops()
-    T, B, four_h = xproj.shape
-    H = four_h // 4
-    dev = xproj.device
-    w_bf = w_hh.detach().to(torch.bfloat16).t().contiguous()
-    bias = b_hh.detach().float().contiguous()
-    h_out = torch.empty((T, B, H), dtype=torch.bfloat16, device=dev)
-    stream = torch.cuda.current_stream(dev).cuda_stream
-    ops.lstm_seq_fwd(
-        xproj.contiguous().data_ptr(), w_bf.data_ptr(), bias.data_ptr(),
-        h_out.data_ptr(), 0, 0, B, T, H, 0, stream,
-    )
-    return h_out
+    """Inference-only fused forward (no backward saves): the serving path."""
+    return launch_fwd(require_hip_ops().lstm_seq_fwd, xproj, w_hh, b_hh, 4,
+                      save=False)
+
 
 class FusedLSTMLayer(nn.Module):
     """One LSTM layer: hipBLASLt input projection + fused HIP recurrence.
@@ -118,10 +79,7 @@ class FusedLSTMLayer(nn.Module):
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:   # (T, B, F)
         if x.is_cuda:
-            T, B, _ = x.shape
-            pad = (-B) % 64              # kernel batch tile is 64 rows
-            if pad:
-                x = torch.cat([x, x.new_zeros(T, pad, x.shape[2])], dim=1)
+            x, unpad = pad_batch(x, 1)
             # bf16 input projection with f32 master weights (autocast
             # style): halves xproj traffic and makes dW_ih a bf16 GEMM
             bf = torch.bfloat16
@@ -130,7 +88,7 @@ class FusedLSTMLayer(nn.Module):
                 h = _FusedLSTMSeq.apply(xproj, self.w_hh, self.b_hh)
             else:   # serving path: no backward saves
                 h = lstm_seq_infer(xproj, self.w_hh, self.b_hh)
-            return h[:, :B] if pad else h
+            return unpad(h)
         return self._forward_reference(x)
 
     def _forward_reference(self, x: torch.Tensor) -> torch.Tensor:

@@ -26,6 +26,7 @@ import torch
 import torch.nn as nn
 
 from ..ops import require_hip_ops
+from ._recurrent import hh_grads, launch_fwd, pad_batch
 from .lstm import LSTMPricePredictor
 
 
@@ -40,70 +41,32 @@ class _FusedLSTMSeqMulti(torch.autograd.Function):
     @staticmethod
     def forward(ctx, xproj: torch.Tensor, w_hh: torch.Tensor,
                 b_hh: torch.Tensor):
-        ops = require_hip_ops()
-        M, T, B, four_h = xproj.shape
-        H = four_h // 4
-        assert xproj.dtype == torch.bfloat16 and xproj.is_cuda
-        dev = xproj.device
-        w_bf = w_hh.to(torch.bfloat16).contiguous()           # (M, H, 4H)
-        wt_bf = w_bf.transpose(1, 2).contiguous()             # (M, 4H, H)
-        bias = b_hh.float().contiguous()
-        h_out = torch.empty((M, T, B, H), dtype=torch.bfloat16, device=dev)
-        gates = torch.empty((M, T, B, four_h), dtype=torch.bfloat16,
-                            device=dev)
-        c_sav = torch.empty((M, T, B, H), dtype=torch.float32, device=dev)
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        ops.lstm_seq_fwd_multi(
-            xproj.contiguous().data_ptr(), wt_bf.data_ptr(), bias.data_ptr(),
-            h_out.data_ptr(), gates.data_ptr(), c_sav.data_ptr(), M, B, T, H,
-            1, stream,
-        )
+        h_out, gates, c_sav, w_bf = launch_fwd(
+            require_hip_ops().lstm_seq_fwd_multi, xproj, w_hh, b_hh, 4,
+            save=True)
         ctx.save_for_backward(gates, c_sav, h_out, w_bf)
-        ctx.dims = (M, T, B, H)
         return h_out
 
     @staticmethod
     def backward(ctx, grad_h: torch.Tensor):
-        ops = require_hip_ops()
         gates, c_sav, h_out, w_bf = ctx.saved_tensors
-        M, T, B, H = ctx.dims
+        M, T, B, H = h_out.shape
         dev = grad_h.device
-        dgates = torch.empty((M, T, B, 4 * H), dtype=torch.bfloat16,
-                             device=dev)
+        dgates = torch.empty_like(gates)
         dh_up = grad_h.float().contiguous()
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        ops.lstm_seq_bwd_multi(
+        require_hip_ops().lstm_seq_bwd_multi(
             dh_up.data_ptr(), gates.data_ptr(), c_sav.data_ptr(),
-            w_bf.data_ptr(), dgates.data_ptr(), M, B, T, H, stream,
+            w_bf.data_ptr(), dgates.data_ptr(), M, B, T, H,
+            torch.cuda.current_stream(dev).cuda_stream,
         )
-        # dW_hh[m] = sum_t h_{t-1}^T dgates_t — one batched bf16 GEMM
-        h_prev = torch.cat(
-            [torch.zeros((M, 1, B, H), dtype=h_out.dtype, device=dev),
-             h_out[:, :-1]], dim=1,
-        )
-        dg = dgates.reshape(M, T * B, 4 * H)
-        dw_hh = torch.bmm(h_prev.reshape(M, T * B, H).transpose(1, 2),
-                          dg).float()
-        db_hh = dg.sum(dim=1, dtype=torch.float32)
-        return dgates, dw_hh, db_hh
+        return (dgates, *hh_grads(h_out, dgates, time_dim=1))
 
 
 def lstm_seq_infer_multi(xproj: torch.Tensor, w_hh: torch.Tensor,
                          b_hh: torch.Tensor) -> torch.Tensor:
     """Inference-only stacked forward: no backward saves (gates/c)."""
-    ops = require_hip_ops()
-    M, T, B, four_h = xproj.shape
-    H = four_h // 4
-    dev = xproj.device
-    wt_bf = w_hh.detach().to(torch.bfloat16).transpose(1, 2).contiguous()
-    bias = b_hh.detach().float().contiguous()
-    h_out = torch.empty((M, T, B, H), dtype=torch.bfloat16, device=dev)
-    stream = torch.cuda.current_stream(dev).cuda_stream
-    ops.lstm_seq_fwd_multi(
-        xproj.contiguous().data_ptr(), wt_bf.data_ptr(), bias.data_ptr(),
-        h_out.data_ptr(), 0, 0, M, B, T, H, 0, stream,
-    )
-    return h_out
+    return launch_fwd(require_hip_ops().lstm_seq_fwd_multi, xproj, w_hh,
+                      b_hh, 4, save=False)
 
 
 class StackedLSTMLayer(nn.Module):
@@ -132,11 +95,8 @@ class StackedLSTMLayer(nn.Module):
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:   # (M, T, B, F)
         if x.is_cuda:
-            M, T, B, F = x.shape
-            pad = (-B) % 64              # kernel batch tile is 64 rows
-            if pad:
-                x = torch.cat([x, x.new_zeros(M, T, pad, F)], dim=2)
-            Bp = B + pad
+            x, unpad = pad_batch(x, 2)
+            M, T, Bp, F = x.shape
             bf = torch.bfloat16
             xproj = (torch.bmm(x.to(bf).reshape(M, T * Bp, F),
                                self.w_ih.to(bf))
@@ -145,7 +105,7 @@ class StackedLSTMLayer(nn.Module):
                 h = _FusedLSTMSeqMulti.apply(xproj, self.w_hh, self.b_hh)
             else:   # serving path: no backward saves
                 h = lstm_seq_infer_multi(xproj, self.w_hh, self.b_hh)
-            return h[:, :, :B] if pad else h
+            return unpad(h)
         return self._forward_reference(x)
 
     def _forward_reference(self, x: torch.Tensor) -> torch.Tensor:

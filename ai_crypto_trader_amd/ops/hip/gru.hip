@@ -1,7 +1,6 @@
-// Fused GRU sequence kernels — sibling of lstm.hip (same decomposition:
-// batch-tile 64 per block, wave w owns hidden columns [16w,16w+16) across
-// the 3 gates [r|z|n], W_hh LDS-resident, per-step gate GEMM on
-// v_mfma_f32_16x16x32_bf16, h carried through LDS).
+// Fused GRU sequence kernels on the shared recurrent tile core
+// (rnn_tile.hpp: decomposition, fragment mapping, LDS staging, activations,
+// guarded launch), here with the 3 gates [r|z|n].
 //
 // PyTorch GRU semantics (models/gru.py reference):
 //   hp = h @ W_hh + b_hh                      (3H)
@@ -12,26 +11,9 @@
 // the h-side differs only in the n column (da_n * r), applied on the
 // torch side for the dW_hh GEMM (models/gru.py).
 
-#include <stdexcept>
-
-#include "common.hpp"
-
-typedef __bf16 bf16;
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-#define GRU_MT 4            // M-tiles per wave (batch tile = 16*MT rows)
-#define GRU_BM (16 * GRU_MT)
+#include "rnn_tile.hpp"
 
 namespace {
-
-// 1-ulp v_rcp instead of IEEE div (see lstm.hip rationale)
-DEV_INLINE float gsigmoid(float x) {
-    return __builtin_amdgcn_rcpf(1.0f + __expf(-x));
-}
-DEV_INLINE float gtanh(float x) {
-    return 2.0f * __builtin_amdgcn_rcpf(1.0f + __expf(-2.0f * x)) - 1.0f;
-}
 
 template <int H>
 __global__ void __launch_bounds__((H / 16) * 64) gru_seq_fwd_kernel(
@@ -43,43 +25,38 @@ __global__ void __launch_bounds__((H / 16) * 64) gru_seq_fwd_kernel(
     float* __restrict__ hpn_out,       // (T, B, H)   hp_n (pre-r-multiply)
     int B, int T, int save_mode)       // 0 = inference: skip bwd saves
 {
-    constexpr int NW = H / 16;
+    constexpr int NT = (H / 16) * 64;   // threads per block
     constexpr int THREEH = 3 * H;
-    constexpr int HP = H + 8;
+    constexpr int HP = H + RNN_PAD;
 
-    __shared__ bf16 lds_h[GRU_BM * HP];
+    __shared__ bf16 lds_h[RNN_BM * HP];
     __shared__ bf16 lds_w[THREEH * HP];
 
-    const int b0 = blockIdx.x * GRU_BM;
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int w = tid >> 6;
-    const int fr = lane & 15;
-    const int fq = lane >> 4;
+    const int b0 = blockIdx.x * RNN_BM;
+    const RnnLane ln = rnn_lane();
+    const int fq = ln.fq;
 
-    for (int i = tid; i < THREEH * H; i += NW * 64)
-        lds_w[(i / H) * HP + (i % H)] = Wt[i];
-    for (int i = tid; i < GRU_BM * HP; i += NW * 64)
-        lds_h[i] = (bf16)0.0f;
+    rnn_stage<THREEH, H, NT>(lds_w, Wt);    // W_hh^T (3H x H)
+    rnn_zero_h<H, NT>(lds_h);
     __syncthreads();
 
-    const int ncol = 16 * w + fr;
+    const int ncol = ln.ncol();
     float bias_g[3];
 #pragma unroll
     for (int g = 0; g < 3; ++g) bias_g[g] = bias[g * H + ncol];
 
     // previous h at this lane's fragment positions (for h' = ... + z*h)
-    float hprev[GRU_MT][4];
+    float hprev[RNN_MT][4];
 #pragma unroll
-    for (int mt = 0; mt < GRU_MT; ++mt)
+    for (int mt = 0; mt < RNN_MT; ++mt)
 #pragma unroll
         for (int r = 0; r < 4; ++r) hprev[mt][r] = 0.0f;
 
     for (int t = 0; t < T; ++t) {
         const long base_tb = ((long)t * B + b0);
-        f32x4 acc[GRU_MT][3];            // hp = h @ W_hh + b_hh
+        f32x4 acc[RNN_MT][3];            // hp = h @ W_hh + b_hh
 #pragma unroll
-        for (int mt = 0; mt < GRU_MT; ++mt)
+        for (int mt = 0; mt < RNN_MT; ++mt)
 #pragma unroll
             for (int g = 0; g < 3; ++g) {
 #pragma unroll
@@ -89,13 +66,13 @@ __global__ void __launch_bounds__((H / 16) * 64) gru_seq_fwd_kernel(
         for (int ks = 0; ks < H / 32; ++ks) {
             const int k0 = ks * 32 + fq * 8;
 #pragma unroll
-            for (int mt = 0; mt < GRU_MT; ++mt) {
-                const int arow = mt * 16 + fr;
+            for (int mt = 0; mt < RNN_MT; ++mt) {
+                const int arow = mt * 16 + ln.fr;
                 bf16x8 a = *reinterpret_cast<const bf16x8*>(
                     &lds_h[arow * HP + k0]);
 #pragma unroll
                 for (int g = 0; g < 3; ++g) {
-                    const int bcol = g * H + 16 * w + fr;
+                    const int bcol = g * H + ncol;
                     bf16x8 b = *reinterpret_cast<const bf16x8*>(
                         &lds_w[bcol * HP + k0]);
                     acc[mt][g] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
@@ -106,7 +83,7 @@ __global__ void __launch_bounds__((H / 16) * 64) gru_seq_fwd_kernel(
         __syncthreads();
 
 #pragma unroll
-        for (int mt = 0; mt < GRU_MT; ++mt) {
+        for (int mt = 0; mt < RNN_MT; ++mt) {
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const int row = mt * 16 + fq * 4 + r;
@@ -114,10 +91,10 @@ __global__ void __launch_bounds__((H / 16) * 64) gru_seq_fwd_kernel(
                 const float xr = (float)xproj[xb + 0 * H + ncol];
                 const float xz = (float)xproj[xb + 1 * H + ncol];
                 const float xn = (float)xproj[xb + 2 * H + ncol];
-                const float gr = gsigmoid(xr + acc[mt][0][r]);
-                const float gz = gsigmoid(xz + acc[mt][1][r]);
+                const float gr = rnn_sigmoid(xr + acc[mt][0][r]);
+                const float gz = rnn_sigmoid(xz + acc[mt][1][r]);
                 const float hpn = acc[mt][2][r];
-                const float gn = gtanh(xn + gr * hpn);
+                const float gn = rnn_tanh(xn + gr * hpn);
                 const float h =
                     (1.0f - gz) * gn + gz * hprev[mt][r];
                 hprev[mt][r] = h;
@@ -147,36 +124,31 @@ __global__ void __launch_bounds__((H / 16) * 64) gru_seq_bwd_kernel(
     bf16* __restrict__ dgates_out,     // (T, B, 3H) x-side grads
     int B, int T)
 {
-    constexpr int NW = H / 16;
+    constexpr int NT = (H / 16) * 64;
     constexpr int THREEH = 3 * H;
-    constexpr int GP = THREEH + 8;
+    constexpr int GP = THREEH + RNN_PAD;
 
-    __shared__ bf16 lds_dg[GRU_BM * GP];   // h-side dgates (GEMM A operand)
+    __shared__ bf16 lds_dg[RNN_BM * GP];   // h-side dgates (GEMM A operand)
     __shared__ bf16 lds_w[H * GP];
 
-    const int b0 = blockIdx.x * GRU_BM;
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int w = tid >> 6;
-    const int fr = lane & 15;
-    const int fq = lane >> 4;
+    const int b0 = blockIdx.x * RNN_BM;
+    const RnnLane ln = rnn_lane();
+    const int fq = ln.fq;
 
-    for (int i = tid; i < H * THREEH; i += NW * 64)
-        lds_w[(i / THREEH) * GP + (i % THREEH)] = W[i];
+    rnn_stage<H, THREEH, NT>(lds_w, W);
     __syncthreads();
 
-    const int ncol = 16 * w + fr;
-
-    float dhrec[GRU_MT][4];
+    const int ncol = ln.ncol();
+    float dhrec[RNN_MT][4];
 #pragma unroll
-    for (int mt = 0; mt < GRU_MT; ++mt)
+    for (int mt = 0; mt < RNN_MT; ++mt)
 #pragma unroll
         for (int r = 0; r < 4; ++r) dhrec[mt][r] = 0.0f;
 
     for (int t = T - 1; t >= 0; --t) {
         const long base_tb = ((long)t * B + b0);
 #pragma unroll
-        for (int mt = 0; mt < GRU_MT; ++mt) {
+        for (int mt = 0; mt < RNN_MT; ++mt) {
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const int row = mt * 16 + fq * 4 + r;
@@ -212,17 +184,18 @@ __global__ void __launch_bounds__((H / 16) * 64) gru_seq_bwd_kernel(
         __syncthreads();
 
         // dh_prev += dgates_h @ W_hh^T : (64 x 3H) @ (3H x H)
-        f32x4 acc[GRU_MT];
+        f32x4 acc[RNN_MT];
 #pragma unroll
-        for (int mt = 0; mt < GRU_MT; ++mt) acc[mt] = {0.f, 0.f, 0.f, 0.f};
+        for (int mt = 0; mt < RNN_MT; ++mt) acc[mt] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll 3
         for (int ks = 0; ks < THREEH / 32; ++ks) {
             const int k0 = ks * 32 + fq * 8;
 #pragma unroll
-            for (int mt = 0; mt < GRU_MT; ++mt) {
-                const int arow = mt * 16 + fr;
+            for (int mt = 0; mt < RNN_MT; ++mt) {
+                const int arow = mt * 16 + ln.fr;
                 bf16x8 a = *reinterpret_cast<const bf16x8*>(
                     &lds_dg[arow * GP + k0]);
+                // B[k][n] = W_hh[n][k]: row n of W, 8 contiguous k
                 bf16x8 b = *reinterpret_cast<const bf16x8*>(
                     &lds_w[ncol * GP + k0]);
                 acc[mt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
@@ -230,7 +203,7 @@ __global__ void __launch_bounds__((H / 16) * 64) gru_seq_bwd_kernel(
             }
         }
 #pragma unroll
-        for (int mt = 0; mt < GRU_MT; ++mt)
+        for (int mt = 0; mt < RNN_MT; ++mt)
 #pragma unroll
             for (int r = 0; r < 4; ++r) dhrec[mt][r] += acc[mt][r];
         __syncthreads();
@@ -244,42 +217,16 @@ extern "C" void launch_gru_seq_fwd(const void* xproj, const void* Wt,
                                    void* gates_out, float* hpn_out, int B,
                                    int T, int H, int save_mode,
                                    hipStream_t stream) {
-    if (B <= 0 || B % GRU_BM != 0)
-        throw std::runtime_error("gru_fwd: B must be a multiple of 64");
-    dim3 grid(B / GRU_BM);
-    if (H == 64) {
-        hipLaunchKernelGGL(gru_seq_fwd_kernel<64>, grid, dim3(256), 0,
-                           stream, (const bf16*)xproj, (const bf16*)Wt,
-                           bias, (bf16*)h_out, (bf16*)gates_out, hpn_out,
-                           B, T, save_mode);
-    } else if (H == 32) {
-        hipLaunchKernelGGL(gru_seq_fwd_kernel<32>, grid, dim3(128), 0,
-                           stream, (const bf16*)xproj, (const bf16*)Wt,
-                           bias, (bf16*)h_out, (bf16*)gates_out, hpn_out,
-                           B, T, save_mode);
-    } else {
-        throw std::runtime_error("gru_fwd: H must be 32 or 64");
-    }
+    rnn_launch("gru_fwd", gru_seq_fwd_kernel<64>, gru_seq_fwd_kernel<32>, 1,
+               B, H, stream, (const bf16*)xproj, (const bf16*)Wt, bias,
+               (bf16*)h_out, (bf16*)gates_out, hpn_out, B, T, save_mode);
 }
 
 extern "C" void launch_gru_seq_bwd(const float* dh_up, const void* gates,
                                    const float* hpn_sav, const void* h_out,
                                    const void* W, void* dgates_out, int B,
                                    int T, int H, hipStream_t stream) {
-    if (B <= 0 || B % GRU_BM != 0)
-        throw std::runtime_error("gru_bwd: B must be a multiple of 64");
-    dim3 grid(B / GRU_BM);
-    if (H == 64) {
-        hipLaunchKernelGGL(gru_seq_bwd_kernel<64>, grid, dim3(256), 0,
-                           stream, dh_up, (const bf16*)gates, hpn_sav,
-                           (const bf16*)h_out, (const bf16*)W,
-                           (bf16*)dgates_out, B, T);
-    } else if (H == 32) {
-        hipLaunchKernelGGL(gru_seq_bwd_kernel<32>, grid, dim3(128), 0,
-                           stream, dh_up, (const bf16*)gates, hpn_sav,
-                           (const bf16*)h_out, (const bf16*)W,
-                           (bf16*)dgates_out, B, T);
-    } else {
-        throw std::runtime_error("gru_bwd: H must be 32 or 64");
-    }
+    rnn_launch("gru_bwd", gru_seq_bwd_kernel<64>, gru_seq_bwd_kernel<32>, 1,
+               B, H, stream, dh_up, (const bf16*)gates, hpn_sav,
+               (const bf16*)h_out, (const bf16*)W, (bf16*)dgates_out, B, T);
 }

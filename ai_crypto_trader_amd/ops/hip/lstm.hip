@@ -8,51 +8,20 @@
 // hipBLASLt GEMM on the torch side) pre-computed and read as the
 // accumulator init. No Triton, no CUDA shims, no per-step launches.
 //
-// Decomposition (template H, NW = H/16 waves per block):
-//   block = 64-row batch tile; wave w owns hidden columns [16w, 16w+16)
-//   ACROSS all four gates, so a lane holds i,f,g,o for the same (row, n)
-//   and the cell update c = f*c + i*g, h = o*tanh(c) is register-local.
-//   c lives in registers across the whole sequence; h round-trips LDS
-//   (padded stride -> conflict-free b128 fragment reads).
-//
-// Fragment mapping mfma_f32_16x16x32_bf16 (validated on-device by
-// mfma_gemm_test_bf16 vs torch.matmul):
-//   A[m][k]: lane l holds A[l&15][8*(l>>4) + j], j=0..7  (one b128 read)
-//   B[k][n]: lane l holds B[8*(l>>4)+j][l&15]  -> store B n-major so the
-//            8 k-elements are contiguous per lane
-//   C[m][n]: lane l, reg r -> m = (l>>4)*4 + r, n = l&15
+// Tile decomposition, fragment mapping, LDS staging, activations and the
+// guarded launch are the shared recurrent tile core (rnn_tile.hpp), here
+// with the four gates i,f,g,o: a lane holds all four for the same (row, n),
+// so c = f*c + i*g, h = o*tanh(c) is register-local and c lives in
+// registers across the whole sequence.
 //
 // Backward: reverse-time kernel computes the sequential part only
 // (per-step dgates + the dh_rec = dgates @ W_hh^T chain). The big
 // batched reductions dW_hh = sum_t h_{t-1}^T dgates_t, dW_ih, db are
 // single hipBLASLt GEMMs on the torch side (models/lstm.py).
 
-#include <stdexcept>
-#include <string>
-
-#include "common.hpp"
-
-typedef __bf16 bf16;
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-#define LSTM_MT 4           // M-tiles per wave (batch tile = 16*MT rows)
-#define LSTM_BM (16 * LSTM_MT)   // 64-row batch tiles: B/64 blocks per model
-                                 // (1 block/CU at B=16384; the multi-model
-                                 // launchers add a model axis, grid.y)
+#include "rnn_tile.hpp"
 
 namespace {
-
-// 1-ulp v_rcp instead of IEEE div: the gate math is tolerance-tested
-// against PyTorch fp32 (not bitwise), and libm-grade division costs
-// ~10 instrs per gate element per timestep.
-DEV_INLINE float sigmoidf_(float x) {
-    return __builtin_amdgcn_rcpf(1.0f + __expf(-x));
-}
-DEV_INLINE float tanhf_(float x) {
-    // tanh(x) = 2*sigmoid(2x) - 1, rcp as above
-    return 2.0f * __builtin_amdgcn_rcpf(1.0f + __expf(-2.0f * x)) - 1.0f;
-}
 
 // MULTI adds the model axis: blockIdx.y = model over model-major slabs,
 // each exactly the single-model layout. The single-model launchers keep
@@ -67,20 +36,16 @@ __global__ void __launch_bounds__((H / 16) * 64) lstm_seq_fwd_kernel(
     float* __restrict__ c_out,         // (M, T, B, H)
     int B, int T, int save_mode)       // 0: inference (h only), 1: training
 {
-    constexpr int NW = H / 16;          // waves per block
+    constexpr int NT = (H / 16) * 64;   // threads per block
     constexpr int FOURH = 4 * H;
-    constexpr int HP = H + 8;           // padded LDS strides (bank-spread)
-    constexpr int KST = H / 32;         // MFMA K-steps per gate tile
+    constexpr int HP = H + RNN_PAD;
 
-    __shared__ bf16 lds_h[LSTM_BM * HP];
+    __shared__ bf16 lds_h[RNN_BM * HP];
     __shared__ bf16 lds_w[FOURH * HP];
 
-    const int b0 = blockIdx.x * LSTM_BM;
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int w = tid >> 6;             // wave id = hidden sub-column
-    const int fr = lane & 15;           // fragment col
-    const int fq = lane >> 4;           // fragment row group / k group
+    const int b0 = blockIdx.x * RNN_BM;
+    const RnnLane ln = rnn_lane();
+    const int fq = ln.fq;
     if constexpr (MULTI) {
         // per-model bases, 64-bit and wave-uniform: the per-lane index
         // math below is the single-model one
@@ -96,31 +61,27 @@ __global__ void __launch_bounds__((H / 16) * 64) lstm_seq_fwd_kernel(
         bias += model * FOURH;
     }
 
-    // stage W_hh^T (4H x H) into LDS, padded rows
-    for (int i = tid; i < FOURH * H; i += NW * 64)
-        lds_w[(i / H) * HP + (i % H)] = Wt[i];
-    // zero-init h
-    for (int i = tid; i < LSTM_BM * HP; i += NW * 64)
-        lds_h[i] = (bf16)0.0f;
+    rnn_stage<FOURH, H, NT>(lds_w, Wt);     // W_hh^T (4H x H)
+    rnn_zero_h<H, NT>(lds_h);
     __syncthreads();
 
-    const int ncol = 16 * w + fr;       // this lane's hidden column
+    const int ncol = ln.ncol();
     float bias_g[4];
 #pragma unroll
     for (int g = 0; g < 4; ++g) bias_g[g] = bias[g * H + ncol];
 
-    float c_reg[LSTM_MT][4];            // [m_tile][reg] cell state
+    float c_reg[RNN_MT][4];            // [m_tile][reg] cell state
 #pragma unroll
-    for (int mt = 0; mt < LSTM_MT; ++mt)
+    for (int mt = 0; mt < RNN_MT; ++mt)
 #pragma unroll
         for (int r = 0; r < 4; ++r) c_reg[mt][r] = 0.0f;
 
     for (int t = 0; t < T; ++t) {
         // ---- gates = h @ W_hh^T(+) xproj + bias --------------------------
-        f32x4 acc[LSTM_MT][4];          // [m_tile][gate]
+        f32x4 acc[RNN_MT][4];          // [m_tile][gate]
         const long base_tb = ((long)t * B + b0);
 #pragma unroll
-        for (int mt = 0; mt < LSTM_MT; ++mt) {
+        for (int mt = 0; mt < RNN_MT; ++mt) {
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
                 const int col = g * H + ncol;
@@ -134,16 +95,16 @@ __global__ void __launch_bounds__((H / 16) * 64) lstm_seq_fwd_kernel(
             }
         }
 #pragma unroll
-        for (int ks = 0; ks < KST; ++ks) {
+        for (int ks = 0; ks < H / 32; ++ks) {
             const int k0 = ks * 32 + fq * 8;
 #pragma unroll
-            for (int mt = 0; mt < LSTM_MT; ++mt) {
-                const int arow = mt * 16 + fr;
+            for (int mt = 0; mt < RNN_MT; ++mt) {
+                const int arow = mt * 16 + ln.fr;
                 bf16x8 a = *reinterpret_cast<const bf16x8*>(
                     &lds_h[arow * HP + k0]);
 #pragma unroll
                 for (int g = 0; g < 4; ++g) {
-                    const int bcol = g * H + 16 * w + fr;
+                    const int bcol = g * H + ncol;
                     bf16x8 b = *reinterpret_cast<const bf16x8*>(
                         &lds_w[bcol * HP + k0]);
                     acc[mt][g] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
@@ -155,17 +116,17 @@ __global__ void __launch_bounds__((H / 16) * 64) lstm_seq_fwd_kernel(
 
         // ---- cell update + write h ---------------------------------------
 #pragma unroll
-        for (int mt = 0; mt < LSTM_MT; ++mt) {
+        for (int mt = 0; mt < RNN_MT; ++mt) {
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const int row = mt * 16 + fq * 4 + r;
-                const float gi = sigmoidf_(acc[mt][0][r]);
-                const float gf = sigmoidf_(acc[mt][1][r]);
-                const float gg = tanhf_(acc[mt][2][r]);
-                const float go = sigmoidf_(acc[mt][3][r]);
+                const float gi = rnn_sigmoid(acc[mt][0][r]);
+                const float gf = rnn_sigmoid(acc[mt][1][r]);
+                const float gg = rnn_tanh(acc[mt][2][r]);
+                const float go = rnn_sigmoid(acc[mt][3][r]);
                 const float c = gf * c_reg[mt][r] + gi * gg;
                 c_reg[mt][r] = c;
-                const float h = go * tanhf_(c);
+                const float h = go * rnn_tanh(c);
                 const bf16 hb = (bf16)h;
                 lds_h[row * HP + ncol] = hb;
                 if (save_mode) {       // backward saves: ~5x the stores of
@@ -193,21 +154,17 @@ __global__ void __launch_bounds__((H / 16) * 64) lstm_seq_bwd_kernel(
     bf16* __restrict__ dgates_out,     // (M, T, B, 4H)
     int B, int T)
 {
-    constexpr int NW = H / 16;
+    constexpr int NT = (H / 16) * 64;
     constexpr int FOURH = 4 * H;
-    constexpr int HP = H + 8;
-    constexpr int GP = FOURH + 8;
+    constexpr int GP = FOURH + RNN_PAD;
 
-    __shared__ bf16 lds_dg[LSTM_BM * GP];   // dgates tile (A operand)
+    __shared__ bf16 lds_dg[RNN_BM * GP];    // dgates tile (A operand)
     __shared__ bf16 lds_w[H * GP];          // W_hh (B operand: k=4H contig)
 
-    const int b0 = blockIdx.x * LSTM_BM;
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int w = tid >> 6;
-    const int fr = lane & 15;
-    const int fq = lane >> 4;
-    if constexpr (MULTI) {                  // as in the forward kernel
+    const int b0 = blockIdx.x * RNN_BM;
+    const RnnLane ln = rnn_lane();
+    const int fq = ln.fq;
+    if constexpr (MULTI) {                // as in the forward kernel
         const long model = blockIdx.y;
         const long model_tb = model * T * B;
         dh_up += model_tb * H;
@@ -217,23 +174,21 @@ __global__ void __launch_bounds__((H / 16) * 64) lstm_seq_bwd_kernel(
         W += model * (H * FOURH);
     }
 
-    for (int i = tid; i < H * FOURH; i += NW * 64)
-        lds_w[(i / FOURH) * GP + (i % FOURH)] = W[i];
+    rnn_stage<H, FOURH, NT>(lds_w, W);
     __syncthreads();
 
-    const int ncol = 16 * w + fr;
-
-    float dc[LSTM_MT][4];
-    float dhrec[LSTM_MT][4];
+    const int ncol = ln.ncol();
+    float dc[RNN_MT][4];
+    float dhrec[RNN_MT][4];
 #pragma unroll
-    for (int mt = 0; mt < LSTM_MT; ++mt)
+    for (int mt = 0; mt < RNN_MT; ++mt)
 #pragma unroll
         for (int r = 0; r < 4; ++r) { dc[mt][r] = 0.0f; dhrec[mt][r] = 0.0f; }
 
     for (int t = T - 1; t >= 0; --t) {
         const long base_tb = ((long)t * B + b0);
 #pragma unroll
-        for (int mt = 0; mt < LSTM_MT; ++mt) {
+        for (int mt = 0; mt < RNN_MT; ++mt) {
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const int row = mt * 16 + fq * 4 + r;
@@ -245,7 +200,7 @@ __global__ void __launch_bounds__((H / 16) * 64) lstm_seq_bwd_kernel(
                 const float c = c_sav[(base_tb + row) * H + ncol];
                 const float cprev =
                     (t > 0) ? c_sav[((base_tb - B) + row) * H + ncol] : 0.0f;
-                const float tc = tanhf_(c);
+                const float tc = rnn_tanh(c);
                 const float dh =
                     dh_up[(base_tb + row) * H + ncol] + dhrec[mt][r];
                 const float do_ = dh * tc;
@@ -273,15 +228,15 @@ __global__ void __launch_bounds__((H / 16) * 64) lstm_seq_bwd_kernel(
         __syncthreads();
 
         // dh_rec = dgates @ W_hh^T : (BM x 4H) @ (4H x H) -> (BM x H)
-        f32x4 acc[LSTM_MT];
+        f32x4 acc[RNN_MT];
 #pragma unroll
-        for (int mt = 0; mt < LSTM_MT; ++mt) acc[mt] = {0.f, 0.f, 0.f, 0.f};
+        for (int mt = 0; mt < RNN_MT; ++mt) acc[mt] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll 4
         for (int ks = 0; ks < FOURH / 32; ++ks) {
             const int k0 = ks * 32 + fq * 8;
 #pragma unroll
-            for (int mt = 0; mt < LSTM_MT; ++mt) {
-                const int arow = mt * 16 + fr;
+            for (int mt = 0; mt < RNN_MT; ++mt) {
+                const int arow = mt * 16 + ln.fr;
                 bf16x8 a = *reinterpret_cast<const bf16x8*>(
                     &lds_dg[arow * GP + k0]);
                 // B[k][n] = W_hh[n][k]: row n of W, 8 contiguous k
@@ -292,7 +247,7 @@ __global__ void __launch_bounds__((H / 16) * 64) lstm_seq_bwd_kernel(
             }
         }
 #pragma unroll
-        for (int mt = 0; mt < LSTM_MT; ++mt)
+        for (int mt = 0; mt < RNN_MT; ++mt)
 #pragma unroll
             for (int r = 0; r < 4; ++r) dhrec[mt][r] = acc[mt][r];
         __syncthreads();
@@ -331,26 +286,10 @@ static void lstm_fwd_launch(const char* who, const void* xproj,
                             void* gates_out, float* c_out, int M, int B,
                             int T, int H, int save_mode,
                             hipStream_t stream) {
-    if (B <= 0 || B % LSTM_BM != 0)
-        throw std::runtime_error(std::string(who) +
-                                 ": B must be a multiple of 64");
-    if (M < 1 || M > 65535)
-        throw std::runtime_error(std::string(who) +
-                                 ": M must be in [1, 65535]");
-    dim3 grid(B / LSTM_BM, M);
-    if (H == 64) {
-        hipLaunchKernelGGL((lstm_seq_fwd_kernel<64, MULTI>), grid,
-                           dim3(256), 0, stream, (const bf16*)xproj,
-                           (const bf16*)Wt, bias, (bf16*)h_out,
-                           (bf16*)gates_out, c_out, B, T, save_mode);
-    } else if (H == 32) {
-        hipLaunchKernelGGL((lstm_seq_fwd_kernel<32, MULTI>), grid,
-                           dim3(128), 0, stream, (const bf16*)xproj,
-                           (const bf16*)Wt, bias, (bf16*)h_out,
-                           (bf16*)gates_out, c_out, B, T, save_mode);
-    } else {
-        throw std::runtime_error(std::string(who) + ": H must be 32 or 64");
-    }
+    rnn_launch(who, lstm_seq_fwd_kernel<64, MULTI>,
+               lstm_seq_fwd_kernel<32, MULTI>, M, B, H, stream,
+               (const bf16*)xproj, (const bf16*)Wt, bias, (bf16*)h_out,
+               (bf16*)gates_out, c_out, B, T, save_mode);
 }
 
 template <bool MULTI>
@@ -358,24 +297,10 @@ static void lstm_bwd_launch(const char* who, const float* dh_up,
                             const void* gates, const float* c_sav,
                             const void* W, void* dgates_out, int M, int B,
                             int T, int H, hipStream_t stream) {
-    if (B <= 0 || B % LSTM_BM != 0)
-        throw std::runtime_error(std::string(who) +
-                                 ": B must be a multiple of 64");
-    if (M < 1 || M > 65535)
-        throw std::runtime_error(std::string(who) +
-                                 ": M must be in [1, 65535]");
-    dim3 grid(B / LSTM_BM, M);
-    if (H == 64) {
-        hipLaunchKernelGGL((lstm_seq_bwd_kernel<64, MULTI>), grid,
-                           dim3(256), 0, stream, dh_up, (const bf16*)gates,
-                           c_sav, (const bf16*)W, (bf16*)dgates_out, B, T);
-    } else if (H == 32) {
-        hipLaunchKernelGGL((lstm_seq_bwd_kernel<32, MULTI>), grid,
-                           dim3(128), 0, stream, dh_up, (const bf16*)gates,
-                           c_sav, (const bf16*)W, (bf16*)dgates_out, B, T);
-    } else {
-        throw std::runtime_error(std::string(who) + ": H must be 32 or 64");
-    }
+    rnn_launch(who, lstm_seq_bwd_kernel<64, MULTI>,
+               lstm_seq_bwd_kernel<32, MULTI>, M, B, H, stream, dh_up,
+               (const bf16*)gates, c_sav, (const bf16*)W, (bf16*)dgates_out,
+               B, T);
 }
 
 extern "C" void launch_lstm_seq_fwd(const void* xproj, const void* Wt,

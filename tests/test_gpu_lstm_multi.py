@@ -171,9 +171,9 @@ def test_bad_arguments_raise_before_launch(dev):
     ops = _ops()
     s = _stream(dev)
     for M, B, H in [(2, 32, 64), (2, 96, 64), (0, 64, 64), (2, 64, 48)]:
-        with pytest.raises(RuntimeError):
+        with pytest.raises(RuntimeError, match="lstm_fwd_multi: "):
             ops.lstm_seq_fwd_multi(0, 0, 0, 0, 0, 0, M, B, 4, H, 0, s)
-        with pytest.raises(RuntimeError):
+        with pytest.raises(RuntimeError, match="lstm_bwd_multi: "):
             ops.lstm_seq_bwd_multi(0, 0, 0, 0, 0, M, B, 4, H, s)
 
 

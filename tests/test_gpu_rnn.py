@@ -260,12 +260,13 @@ def test_autograd_function_torch_side(dev, G, H):
 def test_gru_bad_arguments_raise_before_launch(dev):
     ops = _ops()
     s = _stream(dev)
+    # one shared guard: every message names its caller
     for B, H in [(32, 64), (96, 64), (0, 64), (-64, 64), (64, 48)]:
-        with pytest.raises(RuntimeError):
+        with pytest.raises(RuntimeError, match="gru_fwd: "):
             ops.gru_seq_fwd(0, 0, 0, 0, 0, 0, B, 4, H, 0, s)
-        with pytest.raises(RuntimeError):
+        with pytest.raises(RuntimeError, match="gru_bwd: "):
             ops.gru_seq_bwd(0, 0, 0, 0, 0, 0, B, 4, H, s)
-        with pytest.raises(RuntimeError):
+        with pytest.raises(RuntimeError, match="lstm_fwd: "):
             ops.lstm_seq_fwd(0, 0, 0, 0, 0, 0, B, 4, H, 0, s)
-        with pytest.raises(RuntimeError):
+        with pytest.raises(RuntimeError, match="lstm_bwd: "):
             ops.lstm_seq_bwd(0, 0, 0, 0, 0, B, 4, H, s)
