@@ -19,7 +19,7 @@ from __future__ import annotations
 import numpy as np
 import torch
 
-from ..ops.ga import ga_evolve_cpu
+from ..ops.ga import check_tournament, ga_evolve_cpu
 from ..parallel import dist as pdist
 from .engine_cpu import run_backtest_cpu
 from .strategy import PARAM_BOUNDS, random_population
@@ -71,7 +71,9 @@ class GAEngine:
         self.pop_per_rank = pop_per_rank
         self.seed = seed
         self.elite_k = min(elite_k, max(pop_per_rank * world // 4, 1))
-        self.tournament = tournament
+        # the GPU evolve kernels hold 1..4 contestants per tournament;
+        # refuse anything else here, before the first generation
+        self.tournament = check_tournament(tournament)
         self.cx_rate = cx_rate
         self.mut_rate = mut_rate
         self.mut_scale = mut_scale

@@ -25,6 +25,30 @@ from ..parallel import dist as pdist
 N_OBS = 12
 N_ACT = 3
 N_STATE = 16
+ENV_MIN_T = 18          # the first step reads candle 17 of the symbol's row
+ENV_MAX_T = 1 << 24     # the candle index is carried in an f32 state slot
+
+
+def _check_env_args(shape, n_envs, ep_len):
+    """Shared by the GPU env and its numpy twin. The kernels start an
+    episode at candle 16 or later and read one candle ahead, so a history
+    shorter than 18 would be read past its end; the candle index lives in
+    an f32 state slot, exact only up to 2^24."""
+    if len(shape) != 3 or shape[2] != 4:
+        raise ValueError(
+            f"candles must be (nsym, T, 4), got {tuple(shape)}")
+    nsym, T = int(shape[0]), int(shape[1])
+    if nsym < 1:
+        raise ValueError("candles must hold at least one symbol")
+    if not ENV_MIN_T <= T <= ENV_MAX_T:
+        raise ValueError(
+            f"T must be in {ENV_MIN_T}..2^24, got {T}: an episode starts "
+            "at candle 16 and reads one ahead, and the candle index is "
+            "kept in an f32 state slot")
+    if int(n_envs) < 1:
+        raise ValueError(f"n_envs must be >= 1, got {n_envs}")
+    if int(ep_len) < 1:
+        raise ValueError(f"ep_len must be >= 1, got {ep_len}")
 
 
 class TradingVecEnv:
@@ -32,7 +56,10 @@ class TradingVecEnv:
 
     def __init__(self, candles: torch.Tensor, n_envs: int = 256,
                  ep_len: int = 1024, fee: float = 0.001, seed: int = 0):
-        assert candles.is_cuda and candles.dtype == torch.float32
+        if not (torch.is_tensor(candles) and candles.is_cuda
+                and candles.dtype == torch.float32):
+            raise ValueError("candles must be a float32 tensor on the GPU")
+        _check_env_args(candles.shape, n_envs, ep_len)
         self.ops = require_hip_ops()
         self.candles = candles.contiguous()
         self.nsym, self.T, _ = candles.shape
@@ -61,9 +88,10 @@ class TradingVecEnv:
         return self.obs
 
     def step(self, actions: torch.Tensor):
+        actions = actions.to(torch.int32).contiguous()
         self.ops.env_step(
             self.candles.data_ptr(), self.state.data_ptr(),
-            actions.to(torch.int32).contiguous().data_ptr(),
+            actions.data_ptr(),
             self.obs.data_ptr(), self.reward.data_ptr(),
             self.done.data_ptr(), self.nsym, self.T, self.n_envs,
             self.ep_len, self.fee, self.seed, self.epoch, self._stream(),
@@ -78,6 +106,7 @@ class TradingVecEnvCPU:
     def __init__(self, candles: np.ndarray, n_envs: int = 8,
                  ep_len: int = 256, fee: float = 0.001, seed: int = 0):
         self.candles = np.asarray(candles, np.float32)
+        _check_env_args(self.candles.shape, n_envs, ep_len)
         self.nsym, self.T, _ = self.candles.shape
         self.n_envs, self.ep_len, self.fee = n_envs, ep_len, fee
         self.seed = seed
@@ -285,15 +314,36 @@ class ActorCritic(nn.Module):
 
 def gae_gpu(rewards, values, dones, gamma=0.99, lam=0.95):
     """(T,E) rewards/dones, (T+1,E) values -> (adv, returns) via the HIP
-    reverse-scan kernel."""
-    ops = require_hip_ops()
+    reverse-scan kernel. Inputs may be any dense or strided view; the
+    outputs are fresh contiguous (T,E) tensors."""
+    if rewards.dim() != 2:
+        raise ValueError(
+            f"rewards must be (T, E), got {tuple(rewards.shape)}")
     T, E = rewards.shape
-    adv = torch.empty_like(rewards)
-    ret = torch.empty_like(rewards)
+    args = (("rewards", rewards, (T, E)), ("values", values, (T + 1, E)),
+            ("dones", dones, (T, E)))
+    for name, t, shape in args:
+        if tuple(t.shape) != shape:
+            raise ValueError(
+                f"{name} must have shape {shape}, got {tuple(t.shape)}")
+        if t.dtype != torch.float32:
+            raise ValueError(f"{name} must be float32, got {t.dtype}")
+    for name, t, _ in args:
+        if not t.is_cuda or t.device != rewards.device:
+            raise ValueError(f"{name} must be on the GPU of rewards")
+    ops = require_hip_ops()
+    # not empty_like: it would keep the strides of a permuted input while
+    # the kernel writes row-major
+    adv = torch.empty((T, E), dtype=torch.float32, device=rewards.device)
+    ret = torch.empty((T, E), dtype=torch.float32, device=rewards.device)
     stream = torch.cuda.current_stream(rewards.device).cuda_stream
-    ops.gae(rewards.contiguous().data_ptr(), values.contiguous().data_ptr(),
-            dones.contiguous().data_ptr(), adv.data_ptr(), ret.data_ptr(),
-            T, E, gamma, lam, stream)
+    # named, so that each copy lives until the launch: the temporary of
+    # x.contiguous().data_ptr() is freed at once and the next copy would be
+    # handed the same block
+    rewards, values, dones = (rewards.contiguous(), values.contiguous(),
+                              dones.contiguous())
+    ops.gae(rewards.data_ptr(), values.data_ptr(), dones.data_ptr(),
+            adv.data_ptr(), ret.data_ptr(), T, E, gamma, lam, stream)
     return adv, ret
 
 

@@ -34,7 +34,9 @@ __global__ void ga_evolve_kernel(
         return;
     }
 
-    // Two tournaments of `tournament` contestants each.
+    // Two tournaments of `tournament` contestants each. They read disjoint
+    // halves of the eight words only for tournament <= 4 (above it they
+    // share draws; ops/ga.py refuses such a call).
     uint64_t ctr = ((uint64_t)i << 20) | (gen & 0xFFFFF);
     Philox4 r0 = philox4x32(seed, ctr, 0);
     Philox4 r1 = philox4x32(seed, ctr, 1);
@@ -47,6 +49,11 @@ __global__ void ga_evolve_kernel(
         int c2 = (int)(rnd[(k + 4) & 7] % (uint32_t)P);
         if (fitness[c2] > fb) { fb = fitness[c2]; pb = c2; }
     }
+    // a tournament in which no contestant beats -1e30 (NaN or -inf
+    // fitness, or tournament == 0) would leave no parent and index pop
+    // before its first row: fall back to the child's own slot
+    if (pa < 0) pa = i;
+    if (pb < 0) pb = i;
 
     // Uniform crossover + gaussian mutation, clipped to bounds.
     for (int j = 0; j < GA_NPARAM; ++j) {
