@@ -24,21 +24,29 @@
 //     {mean, std} in place, and every lane reads its window's slot
 //   - everything else a lane needs of a candle is one 32-byte LDS record,
 //     written by one thread per candle: {close, high, low, change} and
-//     the shared stochastic/Williams/trend vote inputs — two b128
-//     broadcasts off one address, and the close-to-close change is
-//     computed once per block, not once per lane
+//     the four parameter values at which the candle's stochastic and
+//     Williams votes flip (bt_vote_flip) — two b128 broadcasts off one
+//     address; the close-to-close change and the products threshold *
+//     range are computed once per block, not once per lane, and a lane
+//     compares its own four parameters. The trend vote rides in the
+//     third dword of the lane's Bollinger slot (one b96 read)
 //   - EMA/MACD/Wilder-RSI are O(1) register recurrences per candle; the
 //     EMAs are seeded with close[0], so no candle tests t == 0
 //   - the first WARMUP = 4 sub-tiles of a history run the recurrences
 //     only (no table conversion, no votes, no position machine), so the
 //     main lane loop carries no t >= WARMUP test
-//   - the lane loop is the whole cost (15625 candles x ~175 instructions
+//   - the lane loop is the whole cost (15625 candles x ~176 instructions
 //     a wave), so it holds no instruction the result does not need:
 //     bt_max / bt_min instead of canonicalising fmaxf / fminf, the
 //     trailing trigger computed at entry, thread-indexed LDS addresses
-//     rebuilt per tile instead of living through it. 31744 B of LDS and
-//     96 VGPR per lane keep five blocks on a CU; one dword of scratch is
-//     reloaded once per tile (see BtState::load)
+//     rebuilt per tile instead of living through it, and the drawdown
+//     divide behind a division-free test that skips it, bit for bit, on
+//     the candles where it cannot raise max_dd (BtAccum::mark: a wave
+//     needs it on under half of its candles). 31744 B of LDS and 96 VGPR
+//     per lane keep five blocks on a CU — a 1 KB trend array on top,
+//     32768 B, measured 7% slower, as if only four fit — and a dword of
+//     scratch is reloaded once per tile and one per sub-tile, none in the
+//     lane loop (see BtState::load)
 //   - the position state machine (SL/TP/trailing/vote exits — semantics of
 //     trade_executor_service.py:55-399 + binance_ml_strategy.py:489-543)
 //     matches backtesting/engine_cpu.py bit-for-bit (fp-contract off, same
@@ -76,14 +84,15 @@ struct BtState {
     }
 
     // One candle at t >= WARMUP. `c` = {close, high, low, change} and `sv`
-    // = the shared votes, the candle's LDS record; `ms` = {mean, std} of
-    // this lane's Bollinger window at candle t. The EMAs were seeded.
-    __device__ void step(int t, float4 c, float2 ms, float4 sv)
+    // = the four vote thresholds, the candle's LDS record; `trend` = its
+    // trend vote; `ms` = {mean, std} of this lane's Bollinger window at
+    // candle t. The EMAs were seeded.
+    __device__ void step(int t, float4 c, float2 ms, float4 sv, int trend)
     {
 #pragma clang fp contract(off)           // match the numpy f32 reference
         // --- 1+2. indicators, votes ----------------------------------
-        const int net = v.count<false>(
-            t, c.x, v.recur<true>(t, c.x, c.w), ms, sv);
+        const int net = v.count<false, true>(
+            t, c.x, v.recur<true>(t, c.x, c.w), ms, sv, trend);
         // --- 3+4. position, mark to market; this kernel keeps only the
         // metrics, so what the candle did (the event) is dropped
         pos.step<false>(t, net, v.entry_v, v.exit_v, c.x, c.y, c.z);
@@ -148,6 +157,15 @@ __global__ void __launch_bounds__(BT_BLOCK, 5) backtest_kernel(
     // one record per candle: {close, high, low, change}, then the shared
     // votes (bt_shared_votes<true>) — two b128 broadcasts off one address
     __shared__ float4 rec[BT_TILE][2];
+    // The record's ninth dword, the trend vote, has no LDS of its own
+    // (1 KB more makes five blocks a CU's whole 160 KB, and measured 7%
+    // slower, see profiles/backtest_seg64_exact_cuts.json): between
+    // bt_shared_votes and the next staging nothing reads hl, so it rests
+    // there until phase B moves it into the candle's table slots, where a
+    // lane's {mean, std} read picks it up.
+    int* trend = reinterpret_cast<int*>(&hl[0][0]);
+    static_assert(sizeof(int) * BT_TILE <= sizeof(float) * 2 * BT_SPAN,
+                  "the trend votes fit the dead high/low staging");
     // Bollinger table [sub-tile candle][window - 2]; slot 31 is padding
     __shared__ float4 bbtab[BT_BBSUB * BT_MAXWIN];
     // per window slot: the rolling sums between sub-tiles, and 1/w
@@ -210,7 +228,10 @@ __global__ void __launch_bounds__(BT_BLOCK, 5) backtest_kernel(
             sh_sum[ltid] = b.sum;
             sh_sum2[ltid] = b.sum2;
         }
-        bt_shared_votes<true>(t0, tend, chist, hl, &rec[0][0], ltid);
+        const int my_trend =
+            bt_shared_votes<true>(t0, tend, chist, hl, &rec[0][0], ltid);
+        __syncthreads();                 // every thread is done with hl
+        trend[ltid] = my_trend;
         for (int s0 = 0; s0 < tend; s0 += BT_BBSUB) {
             const int send = min(s0 + BT_BBSUB, tend);
             // a warm-up sub-tile lies below WARMUP as a whole
@@ -259,15 +280,17 @@ __global__ void __launch_bounds__(BT_BLOCK, 5) backtest_kernel(
                     const float2 ms = b.stats<false>(0, 0);
                     bbtab[e].x = ms.x;
                     bbtab[e].y = ms.y;
+                    bbtab[e].z =
+                        __int_as_float(trend[s0 + e / BT_MAXWIN]);
                 }
             }
             __syncthreads();             // table visible
             for (int tt = s0; tt < send; ++tt) {
-                // b64 per lane: equal windows broadcast, distinct windows
-                // sit 16 B apart (w and w + 16 share banks: 2-way at most)
+                // b96 per lane, {mean, std, trend}: equal windows
+                // broadcast, distinct windows sit 16 B apart
                 const float4* e = &my_bb[(tt - s0) * BT_MAXWIN];
                 st.step(t0 + tt, rec[tt][0], make_float2(e->x, e->y),
-                        rec[tt][1]);
+                        rec[tt][1], __float_as_int(e->z));
             }
         }
     }

@@ -51,6 +51,14 @@ __device__ __forceinline__ float bt_max_uniform(float uniform, float b)
     return r;
 }
 
+// a product with a wave-uniform factor, kept in a scalar register likewise
+__device__ __forceinline__ float bt_mul_uniform(float uniform, float b)
+{
+    float r;
+    asm("v_mul_f32 %0, %1, %2" : "=v"(r) : "s"(uniform), "v"(b));
+    return r;
+}
+
 // max(x, 0) and max(-x, 0), the negate folded into the instruction: what
 // fmaxf(x, 0.0f) and fmaxf(-x, 0.0f) compile to when x is an arithmetic
 // result, and also when x was loaded (where fmaxf canonicalises first)
@@ -97,9 +105,17 @@ struct BtAccum {
     float equity, max_eq, max_dd;
     float n_trades, wins, gross_p, gross_l;
     float sum_ret, sum_ret2;
+    // mark()'s drawdown guard constant: 1 - 2^-23, or 0 (guard off) for
+    // an initial equity so small that max_eq * max_dd could be subnormal.
+    // max_eq never falls below the initial equity. Wave-uniform.
+    float dd_c;
 
     __device__ void init(float initial_equity)
     {
+        // readfirstlane: the select is a vector instruction, and without
+        // it the constant would occupy a VGPR through the candle loop
+        dd_c = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(
+            (initial_equity >= 0x1p-100f) ? 0x1.fffffcp-1f : 0.0f)));
         equity = initial_equity; max_eq = initial_equity; max_dd = 0.f;
         n_trades = wins = gross_p = gross_l = 0.f;
         sum_ret = sum_ret2 = 0.f;
@@ -121,7 +137,23 @@ struct BtAccum {
         sum_ret2 += r * r;
         equity = new_eq;
         max_eq = bt_max(max_eq, equity);
-        max_dd = bt_max(max_dd, (max_eq - equity) / max_eq);
+        // The drawdown quotient only matters on the few candles where it
+        // exceeds max_dd, so a division-free test skips it on the others,
+        // bit for bit: with m = max_eq, d = max_dd, x = m - equity and
+        // g = fl(d * dd_c), a skip needs x <= fl(m * g), and
+        //   fl(m * g) <= m * d * (1 - 2^-23) * (1 + 2^-24)^2 < m * d,
+        // hence x / m < d; correctly rounded division is monotone and d
+        // is representable, so fl(x / m) <= d and the max is a no-op.
+        // The two roundings are relative only where no product is
+        // subnormal: d is 0 or at least 2^-24 (a positive x = fl(m - e)
+        // is at least half an ulp of m), so d * dd_c never is, and m * g
+        // is not while m >= 2^-100 — init() switches the guard off below
+        // that. d == 0 (or the guard off) gives the threshold 0: only
+        // x == 0 skips, where the quotient is 0 too. A NaN in x or in
+        // the threshold fails the compare and takes the divide.
+        const float x = max_eq - equity;
+        if (!(x <= max_eq * bt_mul_uniform(dd_c, max_dd)))
+            max_dd = bt_max(max_dd, x / max_eq);
     }
 
     __device__ void finalize(float* __restrict__ out, int T) const

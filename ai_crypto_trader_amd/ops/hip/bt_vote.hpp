@@ -179,10 +179,13 @@ struct VoteState {
     // Part 3, the 6-indicator TradingSignal vote count: net = buys -
     // sells (0 before WARMUP). `ms` is BollState::stats() of this
     // strategy's window at candle t. WARM_TEST = false is for a caller
-    // that only comes here with t >= WARMUP.
-    template <bool WARM_TEST = true>
+    // that only comes here with t >= WARMUP. `sv` is the candle's
+    // bt_shared_votes entry: {st_num, wl_num, srange, trend}, or with
+    // THETA = true the four thresholds of bt_shared_votes<true> and the
+    // trend on its own — four compares without their four multiplies.
+    template <bool WARM_TEST = true, bool THETA = false>
     __device__ int count(int t, float close, Osc o, float2 ms,
-                         float4 sv) const
+                         float4 sv, int trend = 0) const
     {
 #pragma clang fp contract(off)           // match the numpy f32 reference
         float band = bb_k * ms.y;
@@ -194,16 +197,19 @@ struct VoteState {
         if (!WARM_TEST || t >= BT_WARMUP) {
             int buy = (o.rsi_num < rsi_os * o.rsi_den) +
                       (o.macd_hist > 0.0f) +
-                      (bb_num < bb_bth * bb_den) +
-                      (sv.x < stoch_os * sv.z) +
-                      (sv.y < will_os * sv.z);
+                      (bb_num < bb_bth * bb_den);
             int sell = (o.rsi_num > rsi_ob * o.rsi_den) +
                        (o.macd_hist < 0.0f) +
-                       (bb_num > bb_sth * bb_den) +
-                       (sv.x > stoch_ob * sv.z) +
-                       (sv.y > will_ob * sv.z);
+                       (bb_num > bb_sth * bb_den);
+            if (THETA) {
+                buy += (stoch_os >= sv.x) + (will_os >= sv.z);
+                sell += (stoch_ob <= sv.y) + (will_ob <= sv.w);
+            } else {
+                buy += (sv.x < stoch_os * sv.z) + (sv.y < will_os * sv.z);
+                sell += (sv.x > stoch_ob * sv.z) + (sv.y > will_ob * sv.z);
+            }
             // sixth vote: the shared trend, already +1 / -1 / 0
-            net = buy - sell + __float_as_int(sv.w);
+            net = buy - sell + (THETA ? trend : __float_as_int(sv.w));
         }
         return net;
     }
@@ -250,6 +256,73 @@ __device__ inline void bt_stage_tile(
     __syncthreads();
 }
 
+// The ordered-integer image of f32: an involution between a float's bits
+// and an int that orders as the floats do, -0 and +0 both at 0. The finite
+// floats are [-BT_KEY_INF + 1, BT_KEY_INF - 1]; +-BT_KEY_INF are +-inf.
+#define BT_KEY_INF 0x7f800000
+__device__ __forceinline__ int bt_key(int k)
+{
+    return k >= 0 ? k : (int)(0x80000000u - (unsigned)k);
+}
+
+// Where a stochastic / Williams vote flips. A lane votes on
+// num < fl(p * s) (buy) and num > fl(p * s) (sell) with its own parameter
+// p; num and s > 0 belong to the candle. Rounded multiplication by s > 0
+// is monotone in p, so Q(p) = SELL ? !(num > fl(p * s)) : num < fl(p * s)
+// is false below some float and true from it on. Returns the key of the
+// first float with Q true, BT_KEY_INF if no finite one has it. So
+//   buy:  num < fl(p * s)  <=>  p >= float(key)
+//   sell: num > fl(p * s)  <=>  p <= float(key - 1)    (-inf if none)
+// for every finite p. The search probes Q with the very multiply the lanes
+// used: it starts at the quotient estimate `est`, gallops off it in
+// doubling steps and bisects — two or three probes where the product is a
+// normal number, at most 64 wherever it underflows, overflows or the
+// estimate is useless. Exact for every finite num and every s > 0.
+template <bool SELL>
+__device__ inline int bt_vote_flip(float num, float s, float est)
+{
+#pragma clang fp contract(off)
+    auto Q = [&](int k) {
+        const float f = __int_as_float(bt_key(k)) * s;
+        return SELL ? !(num > f) : (num < f);
+    };
+    const int KLOW = -BT_KEY_INF, KHIGH = BT_KEY_INF;   // virtual ends
+    const int k0 = min(max(bt_key(__float_as_int(est)), KLOW + 1), KHIGH - 1);
+    int lo, hi;                       // Q(lo) false, Q(hi) true, or virtual
+    unsigned step = 1;
+    if (Q(k0)) {
+        hi = k0; lo = KLOW;
+        while (step < (unsigned)hi - (unsigned)KLOW) {
+            const int c = hi - (int)step;
+            if (!Q(c)) { lo = c; break; }
+            hi = c; step <<= 1;
+        }
+    } else {
+        lo = k0; hi = KHIGH;
+        while (step < (unsigned)KHIGH - (unsigned)lo) {
+            const int c = lo + (int)step;
+            if (Q(c)) { hi = c; break; }
+            lo = c; step <<= 1;
+        }
+    }
+    while ((unsigned)hi - (unsigned)lo > 1u) {
+        const int mid = lo + (int)(((unsigned)hi - (unsigned)lo) >> 1);
+        if (Q(mid)) hi = mid; else lo = mid;
+    }
+    return hi;
+}
+
+// {theta_buy, theta_sell} of one numerator: the lane's buy vote is
+// p >= theta_buy, its sell vote p <= theta_sell
+__device__ inline float2 bt_vote_thresholds(float num, float s, float inv_s)
+{
+#pragma clang fp contract(off)
+    const float est = num * inv_s;
+    return make_float2(
+        __int_as_float(bt_key(bt_vote_flip<false>(num, s, est))),
+        __int_as_float(bt_key(bt_vote_flip<true>(num, s, est) - 1)));
+}
+
 // Param-independent shared vote inputs of tile candles [t0, t0 + tend),
 // one thread per candle (strategy.py step-1 spec: every lane of a symbol
 // shares them), packed {st_num, wl_num, srange, trend}: st_num =
@@ -264,14 +337,20 @@ __device__ inline void bt_stage_tile(
 // being [BT_TILE][2]: {close, high, low, change} then the votes, so a lane
 // loop reads a whole candle from one address. change = close[t] -
 // close[t - 1], 0 at t = 0; the halo holds the previous tile's last close.
+// Its votes are not {st_num, wl_num, srange} but where each of the four
+// votes on them flips (bt_vote_thresholds): {stoch buy, stoch sell,
+// Williams buy, Williams sell}, for VoteState::count<., true> — the
+// products p * srange are found once per candle here, not once per lane.
+// The record has no room for the trend: it is returned, the calling
+// thread's candle's (0 past tend), for the caller to place.
 template <bool RECORD = false>
-__device__ inline void bt_shared_votes(
+__device__ inline int bt_shared_votes(
     int t0, int tend, const float* __restrict__ chist,
     const float (*__restrict__ hl)[2], float4* __restrict__ sh_vote,
     int tid = threadIdx.x)
 {
 #pragma clang fp contract(off)
-    if (tid >= tend) return;
+    if (tid >= tend) return 0;
     const int t = t0 + tid;
     const int base = tid + BT_HALO;
     const float cl = chist[base];
@@ -291,11 +370,20 @@ __device__ inline void bt_shared_votes(
     const float sma50 = (float)(s50 / (double)L50);
     const int trend = (cl > sma20 && sma20 > sma50) ? 1
                       : ((cl < sma20 && sma20 < sma50) ? -1 : 0);
-    if (RECORD)
+    const float st_num = 100.0f * (cl - lmin);
+    const float wl_num = -100.0f * (hmax - cl);
+    const float srange = fmaxf(hmax - lmin, BT_EPS);
+    if (RECORD) {
         sh_vote[2 * tid] = make_float4(
             cl, hl[base][0], hl[base][1],
             (t == 0) ? 0.0f : cl - chist[base - 1]);
-    sh_vote[RECORD ? 2 * tid + 1 : tid] = make_float4(
-        100.0f * (cl - lmin), -100.0f * (hmax - cl),
-        fmaxf(hmax - lmin, BT_EPS), __int_as_float(trend));
+        const float inv_s = 1.0f / srange;       // an estimate's worth
+        const float2 st = bt_vote_thresholds(st_num, srange, inv_s);
+        const float2 wl = bt_vote_thresholds(wl_num, srange, inv_s);
+        sh_vote[2 * tid + 1] = make_float4(st.x, st.y, wl.x, wl.y);
+    } else {
+        sh_vote[tid] = make_float4(st_num, wl_num, srange,
+                                   __int_as_float(trend));
+    }
+    return trend;
 }
