@@ -26,6 +26,7 @@ from ..backtesting.strategy import (
 )
 from ..ops import gpu_available
 from .families import FAMILIES
+from .fills import DEFAULT_MAX_FILLS
 from .ledger import DEFAULT_MAX_TRADES
 from .data_manager import HistoricalDataManager
 
@@ -123,12 +124,22 @@ class BacktestEngine:
                      record_equity: bool = False,
                      record_trades: bool = False,
                      max_trades: int = DEFAULT_MAX_TRADES,
-                     equity_stride: int = 1) -> dict:
+                     equity_stride: int = 1,
+                     record_fills: bool = False,
+                     max_fills: int = DEFAULT_MAX_FILLS) -> dict:
         """record_trades (vote machine only) adds the trade ledger to the
         stats: `trades` (backtesting/ledger.py records as dicts, at most
         max_trades), `n_open`, and the trade-derived numbers of
         evaluation.calculate_metrics / calculate_advanced_metrics.
-        equity_stride thins the recorded equity curve (vote machine)."""
+        equity_stride thins the recorded equity curve (vote machine, and a
+        family run with record_fills).
+
+        record_fills (grid / dca families only) adds the fill ledger:
+        `fills` (backtesting/fills.py records as dicts, at most
+        max_fills), `n_records`, `trades` (the fills folded into round
+        trips, FillLedger.round_trips — it needs every fill, so a lane
+        that overflows max_fills raises ValueError), `n_open` and the same
+        trade-derived numbers."""
         df = self.dm.load_market_data(symbol, interval,
                                       n_candles=n_candles)
         candles = self.dm.to_chlv(df.iloc[:n_candles])
@@ -146,10 +157,20 @@ class BacktestEngine:
         if fam is not None and record_trades:
             raise ValueError(
                 f"no trade ledger for the {strategy!r} family: its fills "
-                "are per level / per order, not one position at a time")
+                "are per level / per order, not one position at a time; "
+                "record_fills=True records them")
+        if fam is None and record_fills:
+            raise ValueError(
+                f"no fill ledger for the vote machine ({strategy!r}): it "
+                "holds one position at a time; record_trades=True records "
+                "its trades")
         ledger = None
         t0 = time.perf_counter()
-        if fam is None and (record_trades or record_equity):
+        if record_fills:
+            ledger = self._run_fills(fam, candles, vec, max_fills,
+                                     equity_stride)
+            metrics = ledger.metrics
+        elif fam is None and (record_trades or record_equity):
             ledger = self._run_ledger(candles, vec, max_trades,
                                       equity_stride)
             metrics = ledger.metrics
@@ -171,6 +192,10 @@ class BacktestEngine:
                 stats["equity_stride"] = ledger.equity_stride
             if record_trades:
                 stats.update(self._trade_stats(ledger))
+            if record_fills:
+                stats["fills"] = ledger.fills(0, 0)
+                stats.update(self._trade_stats(
+                    ledger, ledger.round_trips(0, 0)))
         elif record_equity:
             stats["equity_curve"] = out[1][0, 0].tolist()
         self._save(stats)
@@ -194,14 +219,32 @@ class BacktestEngine:
                                 max_trades=max_trades,
                                 equity_stride=equity_stride)
 
+    def _run_fills(self, fam, candles: np.ndarray, pop: np.ndarray,
+                   max_fills: int, equity_stride: int):
+        """A family with the fill ledger: the HIP fills kernel on a GPU,
+        the numpy twin on CPU — the same `FillLedger`, as numpy."""
+        if self.device.startswith("cuda"):
+            import torch
+
+            led = fam.run_gpu_fills(
+                torch.from_numpy(candles).to(self.device),
+                torch.from_numpy(pop).to(self.device),
+                max_fills=max_fills, equity_stride=equity_stride)
+            torch.cuda.synchronize()
+            return led.numpy()
+        return fam.run_cpu_fills(candles, pop, max_fills=max_fills,
+                                 equity_stride=equity_stride)
+
     @staticmethod
-    def _trade_stats(ledger) -> dict:
-        """Lane (0, 0)'s records and what only a trade list can say:
-        avg win/loss, streaks, per-trade expectancy."""
+    def _trade_stats(ledger, trades: list | None = None) -> dict:
+        """Lane (0, 0)'s records (a fill ledger's: its round trips, passed
+        in) and what only a trade list can say: avg win/loss, streaks,
+        per-trade expectancy."""
         from .evaluation import (
             calculate_advanced_metrics, calculate_metrics,
         )
-        trades = ledger.trades(0, 0)
+        if trades is None:
+            trades = ledger.trades(0, 0)
         closed = [t for t in trades if t["reason"] != "open"]
         out = {
             "trades": trades,
@@ -253,11 +296,14 @@ class BacktestEngine:
     def optimize(self, symbol: str, pop_size: int = 256,
                  generations: int = 10, n_candles: int = 20_000,
                  seed: int = 0, strategy: str = "vote",
-                 record_trades: bool = False) -> dict:
+                 record_trades: bool = False,
+                 record_fills: bool = False,
+                 max_fills: int = DEFAULT_MAX_FILLS) -> dict:
         """strategy: "vote" (the vote machine) or a family name ("grid",
         "dca") — the GA then searches that family's parameter space.
         record_trades: the final run of the winner keeps its trade ledger
-        (vote machine only)."""
+        (vote machine only). record_fills: it keeps its fill ledger (a
+        family only)."""
         from .ga_engine import GAEngine
 
         df = self.dm.load_market_data(symbol, n_candles=n_candles)
@@ -276,7 +322,9 @@ class BacktestEngine:
         if fam is not None:
             stats = self.run_backtest(symbol, strategy,
                                       params=fam.params_to_dict(best),
-                                      n_candles=n_candles)
+                                      n_candles=n_candles,
+                                      record_fills=record_fills,
+                                      max_fills=max_fills)
         else:
             stats = self.run_backtest(symbol, "optimized",
                                       params=params_to_dict(best),

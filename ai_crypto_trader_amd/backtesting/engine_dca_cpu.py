@@ -12,6 +12,10 @@ from __future__ import annotations
 import numpy as np
 
 from .engine_cpu import NMETRIC, finalize_metrics
+from .fills import (
+    DEFAULT_MAX_FILLS, KIND_DIP, KIND_SCHEDULED, KIND_SCHEDULED_DIP,
+    KIND_TAKE_PROFIT, FillWriter,
+)
 from .strategy_dca import DCA_NPARAM, DIP_LOOKBACK, FEE, NEVER
 
 
@@ -33,11 +37,19 @@ def run_dca_backtest_cpu(
     *,
     initial_equity: float = 1.0,
     record_equity: bool = False,
+    record_fills: bool = False,
+    max_fills: int = DEFAULT_MAX_FILLS,
+    equity_stride: int = 1,
 ):
     """Run every DCA schedule against every symbol.
 
     Returns metrics (P, nsym, NMETRIC) f32; optionally the full equity
-    curves (P, nsym, T) f32."""
+    curves (P, nsym, T) f32.
+
+    record_fills=True returns a `FillLedger` (backtesting/fills.py)
+    instead: the metrics, up to `max_fills` fill records per lane and the
+    equity sampled every `equity_stride` candles — the twin of
+    ops/hip/backtest_fills.hip's DCA kernel."""
     f32 = np.float32
     candles = np.asarray(candles, dtype=f32)
     population = np.asarray(population, dtype=f32)
@@ -81,6 +93,12 @@ def run_dca_backtest_cpu(
     rmax_all = np.ascontiguousarray(rolling_max_close(candles))
     sym_idx = np.tile(np.arange(nsym), P)
 
+    fw = None
+    if record_fills:
+        assert not record_equity, "the ledger carries its own equity samples"
+        fw = FillWriter(L, T, max_fills, equity_stride)
+        cycle = np.zeros(L, np.int32)          # take-profits so far
+
     # flat lanes divide 0/0 for a tp_price nobody reads
     with np.errstate(divide="ignore", invalid="ignore"):
         for t in range(T):
@@ -98,6 +116,12 @@ def run_dca_backtest_cpu(
             gross_p += np.where(tp_hit, np.maximum(pnl, f32(0.0)), f32(0.0))
             gross_l += np.where(tp_hit, np.maximum(-pnl, f32(0.0)),
                                 f32(0.0))
+            if fw is not None and tp_hit.any():
+                i = np.flatnonzero(tp_hit)
+                fw.put(i, t=t, kind=KIND_TAKE_PROFIT, slot=cycle[i],
+                       price=tp_price[i], units=units[i], cash=proceeds[i],
+                       pnl=pnl[i], units_held=f32(0.0))
+                cycle[i] += 1
             units = np.where(tp_hit, f32(0.0), units)
             invested = np.where(tp_hit, f32(0.0), invested)
 
@@ -116,10 +140,19 @@ def run_dca_backtest_cpu(
             usd = np.minimum(usd, cash)
             buying = (sched | dip) & (usd > 0)
             cash = np.where(buying, cash - usd, cash)
-            units = np.where(buying, units + usd * omf / close, units)
+            du = usd * omf / close
+            units = np.where(buying, units + du, units)
             invested = np.where(buying, invested + usd, invested)
             tp_price = np.where(buying, invested / units * tpk, tp_price)
             t_start = np.where(tp_hit, t + 1, t_start)
+            if fw is not None and buying.any():
+                i = np.flatnonzero(buying)
+                kind = np.where(
+                    dip, np.where(sched, KIND_SCHEDULED_DIP, KIND_DIP),
+                    KIND_SCHEDULED)
+                fw.put(i, t=t, kind=kind[i], slot=cycle[i], price=close[i],
+                       units=du[i], cash=-usd[i], pnl=f32(0.0),
+                       units_held=units[i])
 
             # --- 3. mark to market ---------------------------------------
             new_eq = cash + units * close
@@ -131,11 +164,15 @@ def run_dca_backtest_cpu(
             max_dd = np.maximum(max_dd, (max_eq - equity) / max_eq)
             if record_equity:
                 curves[:, t] = equity
+            if fw is not None:
+                fw.sample(t, equity)
 
     metrics = finalize_metrics(
         T, equity, n_trades, wins, gross_p, gross_l, max_dd, sum_ret,
         sum_ret2
     ).reshape(P, nsym, NMETRIC)
+    if fw is not None:
+        return fw.ledger(metrics, P, nsym)
     if record_equity:
         return metrics, curves.reshape(P, nsym, T)
     return metrics

@@ -15,6 +15,10 @@ from __future__ import annotations
 import numpy as np
 
 from .engine_cpu import NMETRIC, finalize_metrics
+from .fills import (
+    DEFAULT_MAX_FILLS, KIND_BREAKOUT, KIND_BUILD, KIND_BUY, KIND_SELL,
+    FillWriter,
+)
 from .strategy_grid import FEE, GRID_NPARAM, MAX_HALF, MAX_LEVELS
 
 NSLOT = 2 * MAX_HALF
@@ -26,11 +30,19 @@ def run_grid_backtest_cpu(
     *,
     initial_equity: float = 1.0,
     record_equity: bool = False,
+    record_fills: bool = False,
+    max_fills: int = DEFAULT_MAX_FILLS,
+    equity_stride: int = 1,
 ):
     """Run every grid against every symbol.
 
     Returns metrics (P, nsym, NMETRIC) f32; optionally the full equity
-    curves (P, nsym, T) f32."""
+    curves (P, nsym, T) f32.
+
+    record_fills=True returns a `FillLedger` (backtesting/fills.py)
+    instead: the metrics, up to `max_fills` fill records per lane and the
+    equity sampled every `equity_stride` candles — the twin of
+    ops/hip/backtest_fills.hip's grid kernel."""
     f32 = np.float32
     f64 = np.float64
     candles = np.asarray(candles, dtype=f32)
@@ -85,7 +97,12 @@ def run_grid_backtest_cpu(
     low_all = np.ascontiguousarray(candles[:, :, 2])
     sym_idx = np.tile(np.arange(nsym), P)
 
-    def build(idx, c):
+    fw = None
+    if record_fills:
+        assert not record_equity, "the ledger carries its own equity samples"
+        fw = FillWriter(L, T, max_fills, equity_stride)
+
+    def build(idx, c, t):
         """(Re)build the grids of lanes `idx` centred at their close `c`."""
         h, th = H[idx], twoH[idx]
         bb = (cf[idx] * cash[idx] / twoHf[idx]).astype(f32)
@@ -108,6 +125,10 @@ def run_grid_backtest_cpu(
             dn = np.where(g, dn / r, c - f32(j) * step).astype(f32)
             lev[idx[m], h[m] + j] = up[m]
             lev[idx[m], h[m] - j] = dn[m]
+            if fw is not None:         # market fill of slot H + j - 1
+                fw.put(idx[m], t=t, kind=KIND_BUILD, slot=h[m] + j - 1,
+                       price=c[m], units=uu[m], cash=-bb[m], pnl=f32(0.0),
+                       units_held=f32(j) * uu[m])
         fl = valid[idx] & (slots[None, :] >= h[:, None])
         filled[idx] = fl
         initial[idx] = fl
@@ -131,7 +152,7 @@ def run_grid_backtest_cpu(
         for t in range(T):
             close = close_all[sym_idx, t]
             if t == 0:
-                build(all_lanes, close)
+                build(all_lanes, close, t)
             else:
                 high = high_all[sym_idx, t]
                 low = low_all[sym_idx, t]
@@ -148,6 +169,12 @@ def run_grid_backtest_cpu(
                         m, units_total - uk.astype(f64), units_total)
                     book_trade(m, proceeds - b)
                     filled[:, k] &= ~m
+                    if fw is not None:
+                        i = np.flatnonzero(m)
+                        fw.put(i, t=t, kind=KIND_SELL, slot=k,
+                               price=l_sell[i, k], units=uk[i],
+                               cash=proceeds[i], pnl=(proceeds - b)[i],
+                               units_held=units_total[i].astype(f32))
                 # --- 2. buys, descending k -------------------------------
                 for k in np.flatnonzero(buy.any(axis=0))[::-1]:
                     m = buy[:, k] & (cash >= b)
@@ -157,17 +184,30 @@ def run_grid_backtest_cpu(
                         m, units_total + uk.astype(f64), units_total)
                     filled[:, k] |= m
                     initial[:, k] &= ~m
+                    if fw is not None:
+                        i = np.flatnonzero(m)
+                        fw.put(i, t=t, kind=KIND_BUY, slot=k,
+                               price=l_buy[i, k], units=uk[i], cash=-b[i],
+                               pnl=f32(0.0),
+                               units_held=units_total[i].astype(f32))
                 # --- 3. breakout: liquidate at close, rebuild ------------
                 brk = (close > up_thr) | (close < dn_thr)
                 if brk.any():
                     liq = filled & brk[:, None]
                     for k in np.flatnonzero(liq.any(axis=0)):
                         m = liq[:, k]
-                        proceeds = slot_units(k) * close * omf
+                        uk = slot_units(k)
+                        proceeds = uk * close * omf
                         cash = np.where(m, cash + proceeds, cash)
                         book_trade(m, proceeds - b)
+                        if fw is not None:
+                            i = np.flatnonzero(m)
+                            fw.put(i, t=t, kind=KIND_BREAKOUT, slot=k,
+                                   price=close[i], units=uk[i],
+                                   cash=proceeds[i], pnl=(proceeds - b)[i],
+                                   units_held=units_total[i].astype(f32))
                     idx = np.flatnonzero(brk)
-                    build(idx, close[idx])
+                    build(idx, close[idx], t)
 
             # --- 4. mark to market ---------------------------------------
             new_eq = cash + units_total.astype(f32) * close
@@ -179,11 +219,15 @@ def run_grid_backtest_cpu(
             max_dd = np.maximum(max_dd, (max_eq - equity) / max_eq)
             if record_equity:
                 curves[:, t] = equity
+            if fw is not None:
+                fw.sample(t, equity)
 
     metrics = finalize_metrics(
         T, equity, n_trades, wins, gross_p, gross_l, max_dd, sum_ret,
         sum_ret2
     ).reshape(P, nsym, NMETRIC)
+    if fw is not None:
+        return fw.ledger(metrics, P, nsym)
     if record_equity:
         return metrics, curves.reshape(P, nsym, T)
     return metrics

@@ -32,6 +32,27 @@ def _run_dca_gpu(candles, population, **kw):
     return run_dca_backtest_gpu(candles, population, **kw)
 
 
+def _run_grid_fills_cpu(candles, population, **kw):
+    return run_grid_backtest_cpu(candles, population, record_fills=True,
+                                 **kw)
+
+
+def _run_dca_fills_cpu(candles, population, **kw):
+    return run_dca_backtest_cpu(candles, population, record_fills=True, **kw)
+
+
+def _run_grid_fills_gpu(candles, population, **kw):
+    from ..ops.backtest_families import run_grid_fills_gpu
+
+    return run_grid_fills_gpu(candles, population, **kw)
+
+
+def _run_dca_fills_gpu(candles, population, **kw):
+    from ..ops.backtest_families import run_dca_fills_gpu
+
+    return run_dca_fills_gpu(candles, population, **kw)
+
+
 @dataclass(frozen=True)
 class Family:
     name: str
@@ -44,6 +65,10 @@ class Family:
     dict_to_params: Callable
     run_cpu: Callable                   # numpy twin
     run_gpu: Callable                   # HIP op (torch tensors)
+    # the same runs with the fill ledger (backtesting/fills.py): keywords
+    # max_fills, equity_stride, initial_equity; return a FillLedger
+    run_cpu_fills: Callable
+    run_gpu_fills: Callable
 
 
 FAMILIES = {
@@ -52,13 +77,15 @@ FAMILIES = {
         _grid.GRID_PARAM_BOUNDS,
         _grid.clip_grid_params, _grid.random_grid_population,
         _grid.grid_params_to_dict, _grid.dict_to_grid_params,
-        run_grid_backtest_cpu, _run_grid_gpu),
+        run_grid_backtest_cpu, _run_grid_gpu,
+        _run_grid_fills_cpu, _run_grid_fills_gpu),
     "dca": Family(
         "dca", _dca.DCA_NPARAM, _dca.DCA_PARAM_NAMES,
         _dca.DCA_PARAM_BOUNDS,
         _dca.clip_dca_params, _dca.random_dca_population,
         _dca.dca_params_to_dict, _dca.dict_to_dca_params,
-        run_dca_backtest_cpu, _run_dca_gpu),
+        run_dca_backtest_cpu, _run_dca_gpu,
+        _run_dca_fills_cpu, _run_dca_fills_gpu),
 }
 
 

@@ -91,9 +91,12 @@ class ResultAnalyzer:
 
     def trade_analysis(self, stats: dict) -> dict:
         """(:150-225) trade-level aggregates from the stats dict; with a
-        trade ledger (stats["trades"], backtesting/ledger.py) also the
-        per-exit-reason split, durations, avg win/loss and the true
-        per-trade expectancy, over the closed trades."""
+        trade ledger (stats["trades"]: backtesting/ledger.py records, or a
+        grid / dca family's fills folded into round trips,
+        backtesting/fills.py, whose reasons are sell / breakout /
+        take_profit) also the per-exit-reason split, durations, avg
+        win/loss and the true per-trade expectancy, over the closed
+        trades."""
         n = stats.get("n_trades", 0)
         out = {
             "n_trades": n,

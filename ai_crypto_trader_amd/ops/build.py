@@ -24,6 +24,7 @@ SOURCES = [
     "backtest_ledger.hip",
     "backtest_grid.hip",
     "backtest_dca.hip",
+    "backtest_fills.hip",
     "ga.hip",
     "montecarlo.hip",
     "covar.hip",

@@ -23,17 +23,15 @@
 // per candle — gfx950 has no integer divide.
 //
 // Compiler resource report (hipcc -O3, gfx950, -Rpass-analysis=
-// kernel-resource-usage): 50 VGPR, 0 AGPR, 38 SGPR, 0 B scratch, no
+// kernel-resource-usage): 50 VGPR, 0 AGPR, 42 SGPR, 0 B scratch, no
 // spills, 6,656 B LDS/block, occupancy 8 waves/SIMD. Measured rates:
 // docs/KERNELS.md "Strategy families".
+//
+// The lane state machine itself (DcaLane) is in bt_dca.hpp, shared with
+// backtest_fills.hip, which runs it with a recorder that writes one record
+// per order; here it runs with the no-op recorder.
 
-#include "bt_common.hpp"
-
-#define DC_NPARAM 7
-#define DC_LOOKBACK 120          // == strategy_dca.py DIP_LOOKBACK
-#define DC_HALO 128              // >= DC_LOOKBACK - 1
-#define DC_SPAN (BT_TILE + DC_HALO)
-#define DC_NEVER (-(1 << 20))    // == strategy_dca.py NEVER
+#include "bt_dca.hpp"
 
 namespace {
 
@@ -53,29 +51,18 @@ __global__ void __launch_bounds__(BT_BLOCK) backtest_dca_kernel(
     const int tid = threadIdx.x;
     const int p = chunk * BT_BLOCK + tid;
     const bool act = p < P;
-    const float* pr = pop + (long)(act ? p : 0) * DC_NPARAM;
 
-    const float omf = 1.0f - BT_FEE;
-    const int period = max((int)pr[0], 1);
-    const float base = pr[1] * initial_equity;
-    const float four_base = 4.0f * base;
-    const float dipk = 1.0f - pr[2];
-    const float dip_mult = pr[3];
-    const int cooldown = (int)pr[4];
-    const float tpk = 1.0f + pr[5];
-    const bool va = pr[6] > 0.5f;
-
-    float cash = initial_equity, units = 0.f, invested = 0.f;
-    float tp_price = 0.f;
-    int since = 0, nper = 0, last_dip = DC_NEVER;
-    BtAccum acc;
-    acc.init(initial_equity);
+    DcaLane st;
+    DcaNoFills rec;                      // metrics only: no fill records
+    st.load(pop + (long)(act ? p : 0) * DC_NPARAM, initial_equity);
 
     const float4* sym_candles =
         reinterpret_cast<const float4*>(candles + (long)sym * T * 4);
 
     for (int t0 = 0; t0 < T; t0 += BT_TILE) {
         const int tend = min(BT_TILE, T - t0);
+        // bt_dca.hpp's dca_stage_tile, kept in the body (the reason is
+        // there)
         __syncthreads();
         // stage [t0 - HALO, t0 + TILE); -inf left of t=0 (max identity)
         for (int i = tid; i < DC_SPAN; i += BT_BLOCK) {
@@ -99,47 +86,12 @@ __global__ void __launch_bounds__(BT_BLOCK) backtest_dca_kernel(
             tile[tid] = make_float4(chist[base_i], shigh[tid], m, 0.0f);
         }
         __syncthreads();
-        for (int tt = 0; tt < tend; ++tt) {
-            const int t = t0 + tt;
-            const float4 c = tile[tt];       // b128 broadcast
-            const float close = c.x, high = c.y, rmax = c.z;
-            // --- 1. take profit ------------------------------------------
-            if (units > 0.0f && high >= tp_price) {
-                const float proceeds = units * tp_price * omf;
-                cash += proceeds;
-                acc.trade(proceeds - invested);
-                units = 0.0f;
-                invested = 0.0f;
-                since = 0;
-                nper = 0;
-            } else {
-                // --- 2. scheduled / dip buy ------------------------------
-                bool sched = false;
-                if (++since == period) { since = 0; ++nper; sched = true; }
-                const bool dip = (close < rmax * dipk) &&
-                                 (t - last_dip >= cooldown);
-                if (sched || dip) {
-                    float usd = base;
-                    if (sched && va)
-                        usd = fminf(fmaxf(base * (float)nper - units * close,
-                                          0.0f), four_base);
-                    if (dip) { usd = usd * dip_mult; last_dip = t; }
-                    usd = fminf(usd, cash);
-                    if (usd > 0.0f) {
-                        cash -= usd;
-                        units += usd * omf / close;
-                        invested += usd;
-                        tp_price = invested / units * tpk;
-                    }
-                }
-            }
-            // --- 3. mark to market ---------------------------------------
-            acc.mark(cash + units * close);
-        }
+        for (int tt = 0; tt < tend; ++tt)
+            st.step(t0 + tt, tile[tt], rec);     // LDS broadcast reads
     }
 
     if (act)
-        acc.finalize(metrics + ((long)p * nsym + sym) * BT_NMETRIC, T);
+        st.acc.finalize(metrics + ((long)p * nsym + sym) * BT_NMETRIC, T);
 }
 
 }  // namespace

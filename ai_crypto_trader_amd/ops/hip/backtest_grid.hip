@@ -39,155 +39,14 @@
 // spills, 37,888 B LDS/block, occupancy 4 waves/SIMD — LDS-limited, as
 // the arithmetic above predicts. Measured rates and what bounds them:
 // docs/KERNELS.md "Strategy families".
+//
+// The lane state machine itself (GridLane) is in bt_grid.hpp, shared with
+// backtest_fills.hip, which runs it with a recorder that writes one record
+// per fill; here it runs with the no-op recorder.
 
-#include "bt_common.hpp"
-
-#define GR_NPARAM 5
-#define GR_MAXHALF 16            // == strategy_grid.py MAX_HALF
-#define GR_NLEV (2 * GR_MAXHALF + 1)
+#include "bt_grid.hpp"
 
 namespace {
-
-struct GridLane {
-    // params
-    int H, twoH;
-    uint32_t slotmask;
-    float s, cf, up_k, dn_k;
-    bool geo;
-    // grid state
-    uint32_t filled, initial;
-    float b, bomf, u0;
-    float sell_px, buy_px, up_thr, dn_thr;
-    float cash;
-    double units_total;
-    BtAccum acc;
-
-    __device__ void load(const float* __restrict__ pr, float initial_equity)
-    {
-#pragma clang fp contract(off)
-        H = min(max((int)pr[0], 1), GR_MAXHALF);
-        twoH = 2 * H;
-        slotmask = (twoH >= 32) ? 0xffffffffu : ((1u << twoH) - 1u);
-        s = pr[1];
-        geo = pr[2] > 0.5f;
-        cf = pr[3];
-        up_k = 1.0f + pr[4];
-        dn_k = 1.0f - pr[4];
-        filled = initial = 0u;
-        b = bomf = u0 = 0.f;
-        sell_px = buy_px = up_thr = dn_thr = 0.f;
-        cash = initial_equity;
-        units_total = 0.0;
-        acc.init(initial_equity);
-    }
-
-    // units held by filled slot k
-    __device__ float slot_units(const float (*lev)[BT_BLOCK], int tid,
-                                int k) const
-    {
-#pragma clang fp contract(off)
-        return ((initial >> k) & 1u) ? u0 : bomf / lev[k][tid];
-    }
-
-    // reload the two cursor levels from the table
-    __device__ void refresh_px(const float (*lev)[BT_BLOCK], int tid)
-    {
-        const uint32_t empt = ~filled & slotmask;
-        sell_px = filled ? lev[__ffs((int)filled)][tid] : INFINITY;
-        buy_px = empt ? lev[31 - __clz((int)empt)][tid] : -INFINITY;
-    }
-
-    __device__ void build(float (*lev)[BT_BLOCK], int tid, float close)
-    {
-#pragma clang fp contract(off)
-        const float omf = 1.0f - BT_FEE;
-        b = cf * cash / (float)twoH;
-        bomf = b * omf;
-        u0 = bomf / close;
-        cash = cash - (float)H * b;
-        units_total = (double)H * (double)u0;
-        lev[H][tid] = close;
-        float up = close, dn = close;
-        if (geo) {
-            const float r = 1.0f + s;
-            for (int j = 1; j <= H; ++j) {
-                up = up * r;
-                dn = dn / r;
-                lev[H + j][tid] = up;
-                lev[H - j][tid] = dn;
-            }
-        } else {
-            const float step = close * s;
-            for (int j = 1; j <= H; ++j) {
-                up = close + (float)j * step;
-                dn = close - (float)j * step;
-                lev[H + j][tid] = up;
-                lev[H - j][tid] = dn;
-            }
-        }
-        filled = slotmask & ~((1u << H) - 1u);
-        initial = filled;
-        up_thr = up * up_k;
-        dn_thr = dn * dn_k;
-        refresh_px(lev, tid);
-    }
-
-    __device__ void step(float (*lev)[BT_BLOCK], int tid, float close,
-                         float high, float low)
-    {
-#pragma clang fp contract(off)
-        const float omf = 1.0f - BT_FEE;
-        const uint32_t f0 = filled;          // pre-candle fill state
-        bool touched = false;
-        // --- 1. sells, ascending k ---------------------------------------
-        if (high >= sell_px) {
-            uint32_t m = f0;
-            while (m) {
-                const int k = __ffs((int)m) - 1;
-                const float lk1 = lev[k + 1][tid];
-                if (!(high >= lk1)) break;
-                const float uk = slot_units(lev, tid, k);
-                const float proceeds = uk * lk1 * omf;
-                cash += proceeds;
-                units_total -= (double)uk;
-                acc.trade(proceeds - b);
-                filled &= ~(1u << k);
-                m &= m - 1u;
-            }
-            touched = true;
-        }
-        // --- 2. buys, descending k ---------------------------------------
-        if (low <= buy_px) {
-            uint32_t m = ~f0 & slotmask;
-            while (m) {
-                const int k = 31 - __clz((int)m);
-                const float lk = lev[k][tid];
-                if (!(low <= lk) || !(cash >= b)) break;
-                cash -= b;
-                units_total += (double)(bomf / lk);
-                filled |= 1u << k;
-                initial &= ~(1u << k);
-                m &= ~(1u << k);
-            }
-            touched = true;
-        }
-        // --- 3. breakout: liquidate at close, rebuild --------------------
-        if (close > up_thr || close < dn_thr) {
-            uint32_t m = filled;
-            while (m) {
-                const int k = __ffs((int)m) - 1;
-                const float uk = slot_units(lev, tid, k);
-                const float proceeds = uk * close * omf;
-                cash += proceeds;
-                acc.trade(proceeds - b);
-                m &= m - 1u;
-            }
-            build(lev, tid, close);
-        } else if (touched) {
-            refresh_px(lev, tid);
-        }
-    }
-};
 
 // min 4 blocks/CU: what the LDS footprint allows (see header)
 __global__ void __launch_bounds__(BT_BLOCK, 4) backtest_grid_kernel(
@@ -207,6 +66,7 @@ __global__ void __launch_bounds__(BT_BLOCK, 4) backtest_grid_kernel(
     const bool act = p < P;
 
     GridLane st;
+    GridNoFills rec;                     // metrics only: no fill records
     st.load(pop + (long)(act ? p : 0) * GR_NPARAM, initial_equity);
 
     const float4* sym_candles =
@@ -219,8 +79,8 @@ __global__ void __launch_bounds__(BT_BLOCK, 4) backtest_grid_kernel(
         __syncthreads();
         for (int tt = 0; tt < tend; ++tt) {
             const float4 c = tile[tt];          // b128 broadcast
-            if (t0 + tt == 0) st.build(lev, tid, c.x);
-            else st.step(lev, tid, c.x, c.y, c.z);
+            if (t0 + tt == 0) st.build(lev, tid, 0, c.x, rec);
+            else st.step(lev, tid, t0 + tt, c.x, c.y, c.z, rec);
             // --- 4. mark to market -----------------------------------
             st.acc.mark(st.cash + (float)st.units_total * c.x);
         }

@@ -37,6 +37,14 @@ extern "C" void launch_backtest_grid(const float*, const float*, float*, int,
                                      int, int, float, hipStream_t);
 extern "C" void launch_backtest_dca(const float*, const float*, float*, int,
                                     int, int, float, hipStream_t);
+extern "C" void launch_backtest_grid_fills(const float*, const float*, float*,
+                                           int*, float*, float*, int, int,
+                                           int, int, int, int, float,
+                                           hipStream_t);
+extern "C" void launch_backtest_dca_fills(const float*, const float*, float*,
+                                          int*, float*, float*, int, int,
+                                          int, int, int, int, float,
+                                          hipStream_t);
 extern "C" void launch_ga_evolve_generic(const float*, const float*,
                                          const int*, const float*, float*,
                                          int, int, int, int, float, float,
@@ -257,6 +265,42 @@ PYBIND11_MODULE(_hip_ops, m) {
           py::arg("candles"), py::arg("pop"), py::arg("metrics"),
           py::arg("nsym"), py::arg("T"), py::arg("P"),
           py::arg("initial_equity"), py::arg("stream"));
+
+    // backtest_fills.hip: the families plus per-lane fill records (P, nsym,
+    // max_fills, 8 words) and equity samples (nsym, n_samples, P); same
+    // arguments as `backtest_ledger`, and the caller pre-fills the record
+    // buffers likewise (backtesting/fills.py)
+    auto def_fills = [&m](const char* name, auto launch) {
+        m.def(name,
+              [name, launch](uintptr_t candles, uintptr_t pop,
+                             uintptr_t metrics, uintptr_t n_records,
+                             uintptr_t records, uintptr_t equity, int nsym,
+                             int T, int P, int max_fills, int stride,
+                             int n_samples, float initial_equity,
+                             uintptr_t stream) {
+                  // the kernel writes exactly ceil(T / stride) samples
+                  if (nsym < 1 || T < 1 || P < 1 || max_fills < 1 ||
+                      stride < 1 || n_samples != (T + stride - 1) / stride)
+                      throw std::invalid_argument(
+                          std::string(name) + ": bad shape arguments");
+                  launch(reinterpret_cast<const float*>(candles),
+                         reinterpret_cast<const float*>(pop),
+                         reinterpret_cast<float*>(metrics),
+                         reinterpret_cast<int*>(n_records),
+                         reinterpret_cast<float*>(records),
+                         reinterpret_cast<float*>(equity), nsym, T, P,
+                         max_fills, stride, n_samples, initial_equity,
+                         as_stream(stream));
+                  check(hipGetLastError(), name);
+              },
+              py::arg("candles"), py::arg("pop"), py::arg("metrics"),
+              py::arg("n_records"), py::arg("records"), py::arg("equity"),
+              py::arg("nsym"), py::arg("T"), py::arg("P"),
+              py::arg("max_fills"), py::arg("stride"), py::arg("n_samples"),
+              py::arg("initial_equity"), py::arg("stream"));
+    };
+    def_fills("backtest_grid_fills", launch_backtest_grid_fills);
+    def_fills("backtest_dca_fills", launch_backtest_dca_fills);
 
     m.def("ga_evolve_generic",
           [](uintptr_t pop, uintptr_t fitness, uintptr_t order,

@@ -11,6 +11,8 @@ Examples:
   python run_backtest.py optimize --symbol BTCUSDC --pop 256 --generations 10
   python run_backtest.py optimize --symbol BTCUSDC --strategy grid
   python run_backtest.py backtest --symbol BTCUSDC --strategy dca
+  python run_backtest.py backtest --symbol BTCUSDC --strategy grid --fills \
+      --by-regime --plot
   python run_backtest.py list
   python run_backtest.py analyze [--metric sharpe_ratio]
 """
@@ -28,6 +30,9 @@ from ai_crypto_trader_amd.backtesting.engine import (
     STRATEGY_PRESETS, BacktestEngine,
 )
 from ai_crypto_trader_amd.backtesting.families import FAMILIES
+from ai_crypto_trader_amd.backtesting.fills import (
+    DEFAULT_MAX_FILLS, FIELDS as FILL_FIELDS, FILL_KINDS,
+)
 from ai_crypto_trader_amd.backtesting.ledger import (
     DEFAULT_MAX_TRADES, FIELDS, REASONS,
 )
@@ -62,12 +67,18 @@ def main():
                    help="record the trade ledger (vote machine): print "
                         "the per-exit-reason table and write a "
                         "*_trades.csv next to the saved JSON")
+    b.add_argument("--fills", action="store_true",
+                   help="record the fill ledger (grid / dca family): print "
+                        "the per-kind and per-exit-reason tables and write "
+                        "a *_fills.csv next to the saved JSON")
     b.add_argument("--by-regime", action="store_true",
-                   help="with --trades: label the history with the regime "
-                        "detector (HMM) and print the closed trades split "
-                        "by the regime at entry")
+                   help="with --trades or --fills: label the history with "
+                        "the regime detector (HMM) and print the closed "
+                        "trades (round trips) split by the regime at entry")
     b.add_argument("--max-trades", type=int, default=DEFAULT_MAX_TRADES,
                    help="trade records kept (the newest are dropped)")
+    b.add_argument("--max-fills", type=int, default=DEFAULT_MAX_FILLS,
+                   help="fill records kept (the newest are dropped)")
     b.add_argument("--equity-stride", type=int, default=1,
                    help="keep every Nth candle of the equity curve")
 
@@ -92,8 +103,10 @@ def main():
                          "total_return, win_rate, profit_factor")
 
     args = ap.parse_args()
-    if getattr(args, "by_regime", False) and not args.trades:
-        ap.error("--by-regime splits the trade ledger: it needs --trades")
+    if (getattr(args, "by_regime", False)
+            and not (args.trades or args.fills)):
+        ap.error("--by-regime splits the trade ledger: it needs --trades "
+                 "(vote machine) or --fills (grid / dca)")
     dm = HistoricalDataManager(args.data_dir)
 
     if args.cmd == "fetch":
@@ -114,7 +127,8 @@ def main():
             args.symbol, args.strategy, args.interval, args.candles,
             params=params, record_equity=args.plot,
             record_trades=args.trades, max_trades=args.max_trades,
-            equity_stride=args.equity_stride)
+            equity_stride=args.equity_stride, record_fills=args.fills,
+            max_fills=args.max_fills)
         ra = ResultAnalyzer(f"{args.data_dir}/analysis")
         if args.plot:
             p = ra.plot_equity_curve(stats)
@@ -123,7 +137,25 @@ def main():
             if stats.get("trades"):
                 print(f"trade plot -> {ra.plot_trade_analysis(stats)}")
         trades = stats.pop("trades", None)
+        fills = stats.pop("fills", None)
         print(json.dumps(stats, indent=2, default=str))
+        if fills is not None:
+            stats["fills"] = fills
+            print(f"{'fill kind':<14} {'count':>6} {'units':>14} "
+                  f"{'cash':>14}")
+            for kind in FILL_KINDS:
+                rows = [f for f in fills if f["kind"] == kind]
+                if rows:
+                    print(f"{kind:<14} {len(rows):>6} "
+                          f"{sum(f['units'] for f in rows):>14.6f} "
+                          f"{sum(f['cash'] for f in rows):>14.6f}")
+            path = eng.last_saved.with_name(
+                eng.last_saved.stem + "_fills.csv")
+            with open(path, "w", newline="") as f:
+                w = csv.DictWriter(f, fieldnames=list(FILL_FIELDS))
+                w.writeheader()
+                w.writerows(fills)
+            print(f"fills -> {path}")
         if trades is not None:
             stats["trades"] = trades
             if args.by_regime:
@@ -146,12 +178,14 @@ def main():
                     for t in trades]
             ta = ra.trade_analysis(stats)
             print(f"{'exit reason':<14} {'count':>6} {'pnl':>12}")
-            for r in REASONS[1:]:
+            for r in (REASONS[1:] if fills is None
+                      else ("sell", "breakout", "take_profit")):
                 row = ta["by_reason"].get(r, {"count": 0, "pnl": 0.0})
                 print(f"{r:<14} {row['count']:>6} {row['pnl']:>12.6f}")
             print(f"{'closed':<14} {ta['n_closed']:>6} "
                   f"{ta['realized_pnl']:>12.6f}   open {ta['n_open']}, "
-                  f"kept {len(trades)} of {stats['n_records']} records")
+                  f"kept {len(trades if fills is None else fills)} of "
+                  f"{stats['n_records']} records")
             if args.by_regime:
                 print(f"{'regime at entry':<16} {'count':>6} "
                       f"{'win rate':>9} {'pnl':>12}")
@@ -160,13 +194,14 @@ def main():
                         r, {"count": 0, "win_rate": 0.0, "pnl": 0.0})
                     print(f"{r:<16} {row['count']:>6} "
                           f"{row['win_rate']:>9.3f} {row['pnl']:>12.6f}")
-            path = eng.last_saved.with_name(
-                eng.last_saved.stem + "_trades.csv")
-            with open(path, "w", newline="") as f:
-                w = csv.DictWriter(f, fieldnames=[*FIELDS, "duration"])
-                w.writeheader()
-                w.writerows(trades)
-            print(f"trades -> {path}")
+            if fills is None:
+                path = eng.last_saved.with_name(
+                    eng.last_saved.stem + "_trades.csv")
+                with open(path, "w", newline="") as f:
+                    w = csv.DictWriter(f, fieldnames=[*FIELDS, "duration"])
+                    w.writeheader()
+                    w.writerows(trades)
+                print(f"trades -> {path}")
         return
 
     if args.cmd == "optimize":
