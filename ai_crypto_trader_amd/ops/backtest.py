@@ -181,7 +181,9 @@ def run_backtest_continuous_gpu(
     assert candles.is_cuda and population.is_cuda
     assert candles.dtype == torch.float32
     assert population.dtype == torch.float32
-    assert tail % 256 == 0
+    # a shard warm-starts `tail` candles before its RESNAP-aligned body,
+    # and the first such body starts at RESNAP
+    assert tail % 256 == 0 and 0 <= tail <= RESNAP
     candles = candles.contiguous()
     population = population.contiguous()
     nsym, T, _ = candles.shape

@@ -189,6 +189,16 @@ PYBIND11_MODULE(_hip_ops, m) {
           [](uintptr_t candles, uintptr_t pop, uintptr_t eflags,
              uintptr_t xflags, int nsym, int T, int P, int nshards,
              int tail, int shard0, int nlaunch, uintptr_t stream) {
+              // shard s > 0 warm-starts at lo(s) - tail with lo(s) on the
+              // RESNAP grid: lo(s) >= RESNAP >= tail needs every shard
+              // to hold a RESNAP period, and tiles must not straddle lo(s)
+              if (nsym < 1 || T < 1 || P < 1 || nshards < 1 ||
+                  nshards > (T / BT_RESNAP > 1 ? T / BT_RESNAP : 1) ||
+                  tail < 0 || tail > BT_RESNAP || tail % BT_TILE != 0 ||
+                  shard0 < 0 || shard0 >= nshards ||
+                  (nlaunch > 0 && nlaunch > nshards - shard0))
+                  throw std::invalid_argument(
+                      "bt_flags: bad shape or shard arguments");
               launch_bt_flags(
                   reinterpret_cast<const float*>(candles),
                   reinterpret_cast<const float*>(pop),
@@ -207,6 +217,15 @@ PYBIND11_MODULE(_hip_ops, m) {
              uintptr_t xflags, uintptr_t metrics, int nsym, int T, int P,
              float initial_equity, int sym0, int nsym_stride, int t_lo,
              int t_hi, uintptr_t state, uintptr_t stream) {
+              // a partial candle range restores from / saves to `state`
+              if (nsym < 1 || T < 1 || P < 1 || sym0 < 0 ||
+                  (long)sym0 + nsym > nsym_stride || t_lo < 0 ||
+                  t_lo >= t_hi ||
+                  t_hi > T || t_lo % BT_TILE != 0 ||
+                  ((t_lo > 0 || t_hi < T) && state == 0))
+                  throw std::invalid_argument(
+                      "bt_trades: bad shape, symbol-group or candle-range "
+                      "arguments");
               launch_bt_trades(
                   reinterpret_cast<const float*>(candles),
                   reinterpret_cast<const float*>(pop),

@@ -62,6 +62,10 @@ def main():
         return (time.perf_counter() - t0) / iters
 
     nshards = args.nshards or pick_nshards(nsym, T, P, tail=args.tail)
+    # every shard body holds a RESNAP period (the wrapper clamps likewise;
+    # the raw ops below raise on more)
+    max_shards = max(1, T // ops.BT_RESNAP)
+    nshards = min(nshards, max_shards)
     out["nshards"] = nshards
 
     # full continuous pipeline (auto time-group overlap)
@@ -110,7 +114,8 @@ def main():
     # shard-count sweep on the flags kernel
     sweep = {}
     for s in (1, 2, 4, 8, 16, 32):
-        if s > 1 and (T // s) < max(4096, 4 * args.tail):
+        if s > max_shards or (
+                s > 1 and (T // s) < max(4096, 4 * args.tail)):
             continue
         d = timeit(lambda s=s: ops.bt_flags(
             c_t.data_ptr(), p_t.data_ptr(), eflags.data_ptr(),
