@@ -292,6 +292,92 @@ class BacktestEngine:
                      "sharpe": best["sharpe"]},
         }
 
+    # --- one strategy, a basket of symbols, one account -------------------
+    def run_portfolio_backtest(self, symbols: list[str], *,
+                               max_positions: int,
+                               strategy: str = "default",
+                               params: dict | None = None,
+                               use_gpu: bool | None = None,
+                               equity_stride: int = 1,
+                               interval: str = "1m",
+                               n_candles: int = 10_000) -> dict:
+        """One vote-machine strategy trading all `symbols` from one cash
+        account with at most `max_positions` open at once (the portfolio
+        position machine, backtesting/portfolio.py) — where
+        run_multiple_backtests gives every symbol the whole account.
+
+        The symbols' histories are cut to their common length and each is
+        normalised to its first close, as run_backtest does. use_gpu None
+        follows the engine's device. The stats are metrics_to_stats of the
+        portfolio plus `per_symbol` (trades, win rate and realised pnl of
+        each symbol's own exits), `refused_slots` / `refused_cash` (entry
+        signals left untaken because every slot was taken / no cash was
+        left) and, with equity_stride > 0, the sampled `equity_curve`."""
+        from .portfolio import check_shape
+
+        symbols = list(symbols)
+        if strategy in FAMILIES:
+            raise ValueError(
+                f"the portfolio machine trades the vote machine's signals; "
+                f"the {strategy!r} family has no portfolio form")
+        check_shape(len(symbols), int(max_positions), int(equity_stride))
+        if len(set(symbols)) != len(symbols):
+            raise ValueError(f"a symbol is listed twice: {symbols}")
+        frames = [self.dm.load_market_data(s, interval, n_candles=n_candles)
+                  for s in symbols]
+        T = min(n_candles, *(len(df) for df in frames))
+        candles = np.concatenate(
+            [self.dm.to_chlv(df.iloc[:T]) for df in frames], axis=0)
+        self.last_candles = candles
+        preset = dict(STRATEGY_PRESETS.get(strategy, {}))
+        if params:
+            preset.update(params)
+        vec = clip_params(dict_to_params(preset)[None])
+        on_gpu = (self.device.startswith("cuda") if use_gpu is None
+                  else bool(use_gpu))
+        t0 = time.perf_counter()
+        if on_gpu:
+            import torch
+
+            from ..ops.backtest import run_backtest_portfolio_gpu
+            dev = self.device if self.device.startswith("cuda") else "cuda"
+            res = run_backtest_portfolio_gpu(
+                torch.from_numpy(candles).to(dev),
+                torch.from_numpy(vec).to(dev), max_positions=max_positions,
+                equity_stride=equity_stride)
+            torch.cuda.synchronize()
+            res = res.numpy()
+        else:
+            from .engine_portfolio_cpu import run_portfolio_backtest_cpu
+            res = run_portfolio_backtest_cpu(
+                candles, vec, max_positions=max_positions,
+                equity_stride=equity_stride)
+        elapsed = time.perf_counter() - t0
+        stats = metrics_to_stats(res.metrics[0], T, interval)
+        head = "_".join(symbols[:3])
+        more = f"_and{len(symbols) - 3}" if len(symbols) > 3 else ""
+        stats.update({
+            "symbol": f"PORTFOLIO_{head}{more}", "symbols": symbols,
+            "strategy": strategy, "interval": interval, "n_candles": T,
+            "max_positions": int(max_positions),
+            "engine": "cuda" if on_gpu else "cpu",
+            "candles_per_sec": len(symbols) * T / max(elapsed, 1e-9),
+            "params": params_to_dict(vec[0]),
+            "refused_slots": int(res.refused[0, 0]),
+            "refused_cash": int(res.refused[0, 1]),
+            "per_symbol": [
+                {"symbol": s, "n_trades": int(n), "wins": int(w),
+                 "win_rate": float(w) / max(float(n), 1.0),
+                 "gross_profit": float(gp), "gross_loss": float(gl),
+                 "pnl": float(gp) - float(gl)}
+                for s, (n, w, gp, gl) in zip(symbols, res.per_symbol[0])],
+        })
+        if res.equity is not None:
+            stats["equity_curve"] = res.equity[0].tolist()
+            stats["equity_stride"] = res.equity_stride
+        self._save(stats)
+        return stats
+
     # --- GA parameter optimization over the GPU kernel -------------------
     def optimize(self, symbol: str, pop_size: int = 256,
                  generations: int = 10, n_candles: int = 20_000,

@@ -15,6 +15,9 @@ from ..backtesting.ledger import (
     DEFAULT_MAX_TRADES, FIELDS, INT_FIELDS, RECORD_BYTES, Ledger,
     n_equity_samples,
 )
+from ..backtesting.portfolio import (
+    PortfolioResult, check_shape, n_portfolio_samples,
+)
 from ..backtesting.strategy import (
     MAX_WIN, NPARAM, RESNAP, SHARED_HALO, WARMUP,
 )
@@ -131,6 +134,22 @@ def pick_nshards(nsym: int, T: int, P: int, *, target_blocks: int = 6144,
     return min(want, max_shards, 64)
 
 
+def _flag_buffers(ops, nsym: int, nwords: int, P: int, dev):
+    """(eflags, xflags, carry) of this shape from _flag_cache, allocated
+    on a miss — which drops the buffers of any other shape."""
+    key = (nsym, nwords, P, dev.index)
+    bufs = _flag_cache.get(key)
+    if bufs is None or bufs[0].device != dev:
+        eflags = torch.empty((nsym, nwords, P), dtype=torch.int64,
+                             device=dev)
+        xflags = torch.empty_like(eflags)
+        carry = torch.empty((P, nsym, ops.BT_NSTATE),
+                            dtype=torch.float32, device=dev)
+        _flag_cache.clear()      # one shape live at a time (16 GB-class)
+        bufs = _flag_cache[key] = (eflags, xflags, carry)
+    return bufs
+
+
 _pipe_streams: dict = {}
 
 _contract_checked = False
@@ -194,18 +213,7 @@ def run_backtest_continuous_gpu(
     nshards = min(nshards, max(1, T // RESNAP))
     nwords = (T + 63) // 64
     dev = candles.device
-    key = (nsym, nwords, P, dev.index)
-    bufs = _flag_cache.get(key)
-    if bufs is None or bufs[0].device != dev:
-        eflags = torch.empty((nsym, nwords, P), dtype=torch.int64,
-                             device=dev)
-        xflags = torch.empty_like(eflags)
-        carry = torch.empty((P, nsym, ops.BT_NSTATE),
-                            dtype=torch.float32, device=dev)
-        _flag_cache.clear()      # one shape live at a time (16 GB-class)
-        _flag_cache[key] = (eflags, xflags, carry)
-    else:
-        eflags, xflags, carry = bufs
+    eflags, xflags, carry = _flag_buffers(ops, nsym, nwords, P, dev)
     metrics = torch.empty((P, nsym, NMETRIC), dtype=torch.float32,
                           device=dev)
     cptr = candles.data_ptr()
@@ -271,6 +279,64 @@ def run_backtest_continuous_gpu(
     done.record(st)
     cur.wait_event(done)
     return metrics
+
+
+def run_backtest_portfolio_gpu(
+    candles: torch.Tensor,     # (nsym, T, 4) f32 cuda, 1 <= nsym <= 64
+    population: torch.Tensor,  # (P, NPARAM) f32 cuda
+    *,
+    max_positions: int,
+    initial_equity: float = 1.0,
+    equity_stride: int = 0,    # 0 = no equity samples
+    nshards: int = 0,          # 0 = auto
+    tail: int = 2048,
+) -> PortfolioResult:
+    """Each strategy trades the whole basket from one cash account with at
+    most `max_positions` open at once (contract: backtesting/portfolio.py):
+    the vote flags by bt_flags (ops/hip/backtest_tp.hip), then the
+    portfolio position machine (ops/hip/backtest_portfolio.hip) over them,
+    both on the current stream. Returns a PortfolioResult of cuda tensors.
+    CPU twin: engine_portfolio_cpu.run_portfolio_backtest_cpu, equal bit
+    for bit. Shares the flag buffers of run_backtest_continuous_gpu."""
+    ops = require_hip_ops()
+    _check_contract(ops)
+    assert candles.is_cuda and population.is_cuda
+    assert candles.dtype == torch.float32
+    assert population.dtype == torch.float32
+    assert candles.dim() == 3 and candles.shape[2] == 4
+    assert population.dim() == 2 and population.shape[1] == NPARAM
+    assert tail % 256 == 0 and 0 <= tail <= RESNAP
+    candles = candles.contiguous()
+    population = population.contiguous()
+    nsym, T, _ = candles.shape
+    P = population.shape[0]
+    max_positions, equity_stride = int(max_positions), int(equity_stride)
+    check_shape(nsym, max_positions, equity_stride)
+    assert T >= 1 and P >= 1
+    if nshards <= 0:
+        nshards = pick_nshards(nsym, T, P, tail=tail)
+    nshards = min(nshards, max(1, T // RESNAP))
+    nwords = (T + 63) // 64
+    dev = candles.device
+    eflags, xflags, _carry = _flag_buffers(ops, nsym, nwords, P, dev)
+    n_samples = n_portfolio_samples(T, equity_stride)
+    metrics = torch.empty((P, NMETRIC), dtype=torch.float32, device=dev)
+    per_symbol = torch.empty((P, nsym, 4), dtype=torch.float32, device=dev)
+    refused = torch.empty((P, 2), dtype=torch.int32, device=dev)
+    equity = (torch.empty((P, n_samples), dtype=torch.float32, device=dev)
+              if equity_stride else None)
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    ops.bt_flags(candles.data_ptr(), population.data_ptr(),
+                 eflags.data_ptr(), xflags.data_ptr(), nsym, T, P, nshards,
+                 tail, 0, nshards, stream)
+    ops.bt_portfolio(
+        candles.data_ptr(), population.data_ptr(), eflags.data_ptr(),
+        xflags.data_ptr(), metrics.data_ptr(), per_symbol.data_ptr(),
+        refused.data_ptr(), equity.data_ptr() if equity_stride else 0,
+        nsym, T, P, max_positions, float(initial_equity), equity_stride,
+        n_samples, stream)
+    return PortfolioResult(metrics, per_symbol, refused, equity,
+                           equity_stride)
 
 
 def fitness_from_metrics(metrics: torch.Tensor) -> torch.Tensor:

@@ -21,6 +21,7 @@ SO_PATH = OPS_DIR / "_hip_ops.so"
 SOURCES = [
     "backtest.hip",
     "backtest_tp.hip",
+    "backtest_portfolio.hip",
     "backtest_ledger.hip",
     "backtest_grid.hip",
     "backtest_dca.hip",

@@ -24,6 +24,11 @@ extern "C" void launch_bt_trades(const float*, const float*,
                                  const unsigned long long*, float*, int,
                                  int, int, float, int, int, int, int,
                                  float*, hipStream_t);
+extern "C" void launch_bt_portfolio(const float*, const float*,
+                                    const unsigned long long*,
+                                    const unsigned long long*, float*,
+                                    float*, int*, float*, int, int, int,
+                                    int, float, int, int, hipStream_t);
 extern "C" void launch_backtest(const float*, const float*, float*, int, int,
                                 int, float, hipStream_t);
 extern "C" void launch_backtest_ledger(const float*, const float*, float*,
@@ -241,6 +246,46 @@ PYBIND11_MODULE(_hip_ops, m) {
           py::arg("T"), py::arg("P"), py::arg("initial_equity"),
           py::arg("sym0"), py::arg("nsym_stride"), py::arg("t_lo"),
           py::arg("t_hi"), py::arg("state"), py::arg("stream"));
+
+    // backtest_portfolio.hip: the portfolio position machine over the
+    // bt_flags bitmaps (backtesting/portfolio.py). metrics (P, NMETRIC),
+    // per_symbol (P, nsym, 4), refused (P, 2) i32, equity (P, n_samples)
+    // sampled as backtest_ledger's; stride 0 = no equity, n_samples 0
+    m.def("bt_portfolio",
+          [](uintptr_t candles, uintptr_t pop, uintptr_t eflags,
+             uintptr_t xflags, uintptr_t metrics, uintptr_t per_symbol,
+             uintptr_t refused, uintptr_t equity, int nsym, int T, int P,
+             int max_positions, float initial_equity, int stride,
+             int n_samples, uintptr_t stream) {
+              // one wave lane per symbol; exactly ceil(T / stride) samples
+              if (nsym < 1 || nsym > 64 || T < 1 || P < 1 ||
+                  max_positions < 1 || max_positions > nsym || stride < 0 ||
+                  n_samples !=
+                      (stride > 0 ? (int)(((long)T + stride - 1) / stride)
+                                  : 0) ||
+                  (stride > 0 && equity == 0))
+                  throw std::invalid_argument(
+                      "bt_portfolio: bad shape, max_positions or "
+                      "equity-sample arguments");
+              launch_bt_portfolio(
+                  reinterpret_cast<const float*>(candles),
+                  reinterpret_cast<const float*>(pop),
+                  reinterpret_cast<const unsigned long long*>(eflags),
+                  reinterpret_cast<const unsigned long long*>(xflags),
+                  reinterpret_cast<float*>(metrics),
+                  reinterpret_cast<float*>(per_symbol),
+                  reinterpret_cast<int*>(refused),
+                  reinterpret_cast<float*>(equity), nsym, T, P,
+                  max_positions, initial_equity, stride, n_samples,
+                  as_stream(stream));
+              check(hipGetLastError(), "bt_portfolio launch");
+          },
+          py::arg("candles"), py::arg("pop"), py::arg("eflags"),
+          py::arg("xflags"), py::arg("metrics"), py::arg("per_symbol"),
+          py::arg("refused"), py::arg("equity"), py::arg("nsym"),
+          py::arg("T"), py::arg("P"), py::arg("max_positions"),
+          py::arg("initial_equity"), py::arg("stride"),
+          py::arg("n_samples"), py::arg("stream"));
 
     m.def("ga_evolve",
           [](uintptr_t pop, uintptr_t fitness, uintptr_t order,

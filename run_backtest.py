@@ -13,6 +13,8 @@ Examples:
   python run_backtest.py backtest --symbol BTCUSDC --strategy dca
   python run_backtest.py backtest --symbol BTCUSDC --strategy grid --fills \
       --by-regime --plot
+  python run_backtest.py backtest --portfolio BTCUSDC,ETHUSDC,SOLUSDC \
+      --max-positions 2 --plot
   python run_backtest.py list
   python run_backtest.py analyze [--metric sharpe_ratio]
 """
@@ -51,7 +53,17 @@ def main():
     f.add_argument("--social", action="store_true")
 
     b = sub.add_parser("backtest", help="run a backtest")
-    b.add_argument("--symbol", required=True)
+    b.add_argument("--symbol", default=None,
+                   help="required unless --portfolio is given")
+    b.add_argument("--portfolio", type=str, default=None,
+                   metavar="SYM1,SYM2,...",
+                   help="trade this basket of symbols (at most 64) with one "
+                        "vote-machine strategy from ONE cash account: "
+                        "prints the portfolio stats, the per-symbol table "
+                        "and how many entry signals went untaken")
+    b.add_argument("--max-positions", type=int, default=None,
+                   help="with --portfolio: positions open at once "
+                        "(default: all symbols)")
     b.add_argument("--strategy", default="default",
                    choices=sorted([*STRATEGY_PRESETS, *FAMILIES]),
                    help="a vote-machine preset, or the strategy family "
@@ -107,6 +119,15 @@ def main():
             and not (args.trades or args.fills)):
         ap.error("--by-regime splits the trade ledger: it needs --trades "
                  "(vote machine) or --fills (grid / dca)")
+    if args.cmd == "backtest":
+        if args.portfolio is None and args.symbol is None:
+            ap.error("backtest needs --symbol (or --portfolio SYM1,SYM2,...)")
+        if args.portfolio is not None and (
+                args.symbol or args.trades or args.fills):
+            ap.error("--portfolio takes the place of --symbol and keeps no "
+                     "per-trade ledger (--trades / --fills)")
+        if args.portfolio is None and args.max_positions is not None:
+            ap.error("--max-positions goes with --portfolio")
     dm = HistoricalDataManager(args.data_dir)
 
     if args.cmd == "fetch":
@@ -123,6 +144,36 @@ def main():
         eng = BacktestEngine(args.data_dir,
                              device="cpu" if args.cpu else None)
         params = json.loads(args.params) if args.params else None
+        if args.portfolio is not None:
+            symbols = [x for x in args.portfolio.split(",") if x]
+            try:
+                stats = eng.run_portfolio_backtest(
+                    symbols,
+                    max_positions=(len(symbols) if args.max_positions is None
+                                   else args.max_positions),
+                    strategy=args.strategy, params=params,
+                    equity_stride=args.equity_stride if args.plot else 0,
+                    interval=args.interval, n_candles=args.candles)
+            except ValueError as e:
+                raise SystemExit(f"--portfolio: {e}")
+            if args.plot:
+                ra = ResultAnalyzer(f"{args.data_dir}/analysis")
+                print(f"plot -> {ra.plot_equity_curve(stats)}")
+                stats.pop("equity_curve", None)
+            rows = stats.pop("per_symbol")
+            print(json.dumps(stats, indent=2, default=str))
+            stats["per_symbol"] = rows
+            print(f"{'symbol':<14} {'trades':>6} {'win rate':>9} "
+                  f"{'pnl':>12}")
+            for r in rows:
+                print(f"{r['symbol']:<14} {r['n_trades']:>6} "
+                      f"{r['win_rate']:>9.3f} {r['pnl']:>12.6f}")
+            print(f"{'portfolio':<14} {stats['n_trades']:>6} "
+                  f"{stats['win_rate']:>9.3f} "
+                  f"{sum(r['pnl'] for r in rows):>12.6f}   entry signals "
+                  f"untaken: {stats['refused_slots']} for slots, "
+                  f"{stats['refused_cash']} for cash")
+            return
         stats = eng.run_backtest(
             args.symbol, args.strategy, args.interval, args.candles,
             params=params, record_equity=args.plot,
